@@ -5,8 +5,14 @@ condition), timed with the search resident on the GPU; value = unique states (re
 counting rule, Search.java:470-490) x steps / wall time, whole job.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload NAME] [--depth D]
+                    [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N ...
+
+A plain run sets up, warms up, times the steps and prints the result line (the roofline object is
+arithmetic on the last step's counters and the committed profiles: no run of its own). --full adds
+the CPU baseline (a ~10 s multithreaded CPU sample and a scalar-oracle sample of the same
+workload). --dump-outputs DIR writes what the last timed search returned as DIR/<name>.npy.
 
 Multi-GPU: one process per GPU; the visited set and frontier are hash-partitioned by
 fingerprint, successors routed to their owner shard per level (RCCL all-to-all over xGMI).
@@ -253,6 +259,29 @@ def random_access_roofline(table_bytes: int, probes_per_s: float, inserts_per_s:
             "source": os.path.relpath(f, ROOT)}
 
 
+def dump_outputs(out_dir: str, res) -> None:
+    """--dump-outputs: the SearchResults of the last timed search as float64 arrays (every count is
+    far below 2^53, so exact). The search has no random input: the same arguments give the same
+    arrays on every run. A few hundred bytes for every workload.
+      per_depth.npy       unique states discovered at each depth
+      summary.npy         [states, successors, max_depth, initial_depth, end_condition, terminal_depth]
+                          (terminal_depth -1: the search ended without a terminal state)
+      terminal_state.npy  the terminal state's packed bytes; not written (and one left by an earlier
+                          run removed) when the search ended without a terminal state"""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    term = (res.invariantViolatingState() or res.goalMatchingState() or res.exceptionalState())
+    np.save(os.path.join(out_dir, "per_depth.npy"), np.asarray(res.per_depth, dtype=np.float64))
+    np.save(os.path.join(out_dir, "summary.npy"),
+            np.asarray([res.states, res.successors, res.max_depth, res.initial_depth, int(res.endCondition()),
+                        term.depth() if term is not None else -1], dtype=np.float64))
+    path = os.path.join(out_dir, "terminal_state.npy")
+    if term is not None:
+        np.save(path, np.frombuffer(term.packed, dtype=np.uint8).astype(np.float64))
+    elif os.path.exists(path):
+        os.unlink(path)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -260,7 +289,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--workload", default="multipaxos")
     ap.add_argument("--depth", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    # --full: everything beyond the headline figure (today the CPU baseline, one GPU only)
+    ap.add_argument("--full", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true")  # with --full: leave the CPU baseline out
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
     # N > 1: the engine's replicated-or-sharded rule (Engine replicate_below): -1 = the cost model
     # (default), 0 = every level hash-sharded (tests), n > 0 = shard frontiers of at least n states
     ap.add_argument("--replicate-below", type=int, default=-1)
@@ -333,6 +365,8 @@ def main():
         per_rank = [None] * world
         dist.all_gather_object(per_rank, mine)
     if rank == 0:
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, res)
         line = {
             "metric": metric_name(args.workload),
             "workload": args.workload,
@@ -362,7 +396,7 @@ def main():
                                          "exchange_rounds", "exchanged", "shard_work_min")},
                 "cost_c_ns": round(stats["cost_c_ns"], 4), "cost_x_us": round(stats["cost_x_us"], 2),
                 "exchanged_all_ranks": sum(r["exchanged"] for r in per_rank), "per_rank": per_rank}
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(proto, settings, min(depth, wl.get("cpu_mt_depth", depth)) if depth >= 0
                                                 else depth, res.per_depth, oracle_args, wl["cpu_depth"], state)
         print(json.dumps(line), flush=True)

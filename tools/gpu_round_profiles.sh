@@ -7,9 +7,9 @@ export TMPDIR=/tmp
 TAG=$1
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-timeout -k 10 300 python3 bench.py > $OUT/bench_c5.json 2> $OUT/bench_c5.err
+timeout -k 10 300 python3 bench.py --full > $OUT/bench_c5.json 2> $OUT/bench_c5.err
 cut -c1-160 $OUT/bench_c5.json
-timeout -k 10 300 python3 bench.py --workload synthetic > $OUT/bench_c3.json 2> $OUT/bench_c3.err
+timeout -k 10 300 python3 bench.py --full --workload synthetic > $OUT/bench_c3.json 2> $OUT/bench_c3.err
 cut -c1-160 $OUT/bench_c3.json
 bash tools/gpu_pmc.sh ${TAG}_c5
 bash tools/gpu_pmc.sh ${TAG}_c3 --workload synthetic

@@ -12,7 +12,7 @@ timeout -k 10 120 python3 -c "import __graft_entry__ as g; g.smoke()" > $OUT/smo
 tail -1 $OUT/smoke.log
 fi
 if [ -z "$NOBENCH" ]; then
-timeout -k 10 300 python3 bench.py ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
+timeout -k 10 300 python3 bench.py --full ${BENCH_ARGS:-} > $OUT/bench.json 2> $OUT/bench.err
 cut -c1-300 $OUT/bench.json
 fi
 echo suite done

@@ -40,7 +40,7 @@ EXPORTED = [
     "dsl_kernel_stats", "dsl_result_free", "dsl_destroy", "dsl_last_error", "dsl_create_with_host_comm",
     "dsl_run_dfs", "dsl_replay", "dsl_human_readable_trace", "dsl_set_dropped",
 ]
-DSL_ABI_VERSION = 5  # include/dslabs_hip.h; load() refuses a library of another layout
+DSL_ABI_VERSION = 6  # include/dslabs_hip.h; load() refuses a library of another layout
 
 
 class dsl_protocol_desc(ctypes.Structure):
@@ -69,6 +69,7 @@ class dsl_settings(ctypes.Structure):
         ("max_frontier_states", ctypes.c_uint64), ("memory_budget_bytes", ctypes.c_uint64),
         ("pool", dsl_predicate * DSL_MAX_POOL),
         ("do_checks", ctypes.c_int32), ("check_sample", ctypes.c_int32),
+        ("max_terminals", ctypes.c_int32), ("reserved", ctypes.c_int32),
     ]
 
 
@@ -98,6 +99,12 @@ class dsl_event(ctypes.Structure):
                 ("fields", ctypes.c_int64 * DSL_MAX_EVENT_FIELDS)]
 
 
+class dsl_terminal(ctypes.Structure):
+    _fields_ = [("end_condition", ctypes.c_int32), ("predicate_index", ctypes.c_int32),
+                ("trace_len", ctypes.c_int32), ("reserved", ctypes.c_int32),
+                ("trace", ctypes.POINTER(dsl_event)), ("state", ctypes.POINTER(ctypes.c_uint8))]
+
+
 class dsl_result(ctypes.Structure):
     _fields_ = [
         ("end_condition", ctypes.c_int32), ("terminal_depth", ctypes.c_int32),
@@ -110,6 +117,8 @@ class dsl_result(ctypes.Structure):
         ("exchanged_states", ctypes.c_uint64), ("level_ms_max", ctypes.c_double),
         ("checks_run", ctypes.c_uint64), ("not_deterministic", ctypes.c_uint64), ("not_idempotent", ctypes.c_uint64),
         ("first_not_deterministic", dsl_event), ("first_not_idempotent", dsl_event),
+        ("terminals_total", ctypes.c_uint64), ("n_terminals", ctypes.c_int32), ("reserved", ctypes.c_int32),
+        ("terminals", ctypes.POINTER(dsl_terminal)),
     ]
 
 

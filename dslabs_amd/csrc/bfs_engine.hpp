@@ -859,6 +859,196 @@ struct BfsEngine : EngineBase {
     return DSL_OK;
   }
 
+  // ---- every terminal of the level that ended the search (dsl_settings.max_terminals) ----------
+  // After the terminal level, while its frontier is still in S.cur: k_list_terminals over the
+  // frontier of one shard (a replicated level) or of every shard (a sharded level), the lists
+  // merged and ordered on the host by (priority, fingerprint), the first max_terminals kept, and
+  // their parent chains walked one history level at a time for all of them (k_hist_gather: one
+  // launch per level and shard, one copy per level). The reported terminal, its find mode and the
+  // visited tables are not touched.
+  struct ListedTrace {
+    int32_t verdict, pred_index;
+    std::vector<uint32_t> events;
+  };
+  std::vector<ListedTrace> term_list;  // the kept terminals of the last search, in order
+  uint64_t term_total = 0;
+  struct DevBufs {
+    std::vector<void*> p;
+    ~DevBufs() {
+      for (void* q : p) (void)hipFree(q);
+    }
+    template <class T>
+    int get(T** out, size_t bytes) {
+      void* q = nullptr;
+      if (hipMalloc(&q, std::max<size_t>(bytes, 16)) != hipSuccess) {
+        (void)hipGetLastError();
+        set_error("terminal list: device allocation of " + std::to_string(bytes) + " bytes failed");
+        return DSL_ERR_HIP;
+      }
+      p.push_back(q);
+      *out = (T*)q;
+      return DSL_OK;
+    }
+  };
+  // One pass over shard S's frontier with room for `cap` terminals; *count and *full come back.
+  int list_pass(Shard& S, int succ_depth, bool incremental, bool owner_filter, uint64_t cap,
+                std::vector<ListedTerminal>& recs, uint64_t* count, uint64_t* full) {
+    DevBufs bufs;
+    ListedTerminal* out = nullptr;
+    unsigned long long* slots = nullptr;
+    unsigned long long* ctr = nullptr;
+    uint64_t buckets = 64;  // a power of two, at least 4x the expected count
+    while (buckets < 4 * cap) buckets <<= 1;
+    DSL_TRY(bufs.get(&out, cap * sizeof(ListedTerminal)));
+    DSL_TRY(bufs.get(&slots, buckets * 64));
+    DSL_TRY(bufs.get(&ctr, 16));
+    DSL_HIP(hipMemsetAsync(slots, 0, buckets * 64, stream));
+    DSL_HIP(hipMemsetAsync(ctr, 0, 16, stream));
+    ListArgs<P> a{};
+    a.cur = S.cur;
+    a.cur_fp = S.cur_fp;
+    const int per = mat_per_max<P>();
+    a.segs.n = (int32_t)S.seg_cnt.size();
+    a.segs.pb = per;
+    for (int q = 0; q < a.segs.n; q++) {
+      a.segs.base[q] = S.seg_base[q];
+      a.segs.cnt[q] = S.seg_cnt[q];
+      a.segs.chunk0[q + 1] = a.segs.chunk0[q] + (S.seg_cnt[q] + per - 1) / per;
+    }
+    a.me = S.gid;
+    a.W = W;
+    a.owner_filter = owner_filter ? 1 : 0;
+    a.depth = succ_depth;
+    a.incremental = incremental ? 1 : 0;
+    a.scratch = Table{slots, buckets - 1, 0, 0};
+    while ((2ull << a.scratch.b0) <= buckets) a.scratch.b0++;  // its own key layout
+    a.out = out;
+    a.cap = cap;
+    a.ctr = ctr;
+    const uint64_t nchunks = a.segs.chunk0[a.segs.n];
+    unsigned long long h[2] = {0, 0};
+    if (nchunks) {
+      const int blocks = (int)std::min<uint64_t>((nchunks + kBlock / 64 - 1) / (kBlock / 64), 4096);
+      const size_t lds = (size_t)(kBlock / 64) * per * NW * 4;
+      hipLaunchKernelGGL(k_list_terminals<P>, dim3(blocks), dim3(kBlock), lds, stream, a, prm, dset);
+      DSL_HIP(hipGetLastError());
+      DSL_HIP(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, stream));
+      DSL_TRY(hsync());
+    }
+    *count = h[0];
+    *full = h[1];
+    recs.resize(std::min<uint64_t>(h[0], cap));
+    if (!recs.empty()) {
+      DSL_HIP(hipMemcpyAsync(recs.data(), out, recs.size() * sizeof(ListedTerminal), hipMemcpyDeviceToHost, stream));
+      DSL_TRY(hsync());
+    }
+    return DSL_OK;
+  }
+  // (priority rank, fingerprint hi, fingerprint lo): the order of the list; term_key is its prefix
+  static bool listed_less(const ListedTerminal& x, const ListedTerminal& y) {
+    if (x.rec.verdict != y.rec.verdict) return x.rec.verdict < y.rec.verdict;
+    if (x.fp.hi != y.fp.hi) return x.fp.hi < y.fp.hi;
+    return x.fp.lo < y.fp.lo;
+  }
+  int list_terminals(int succ_depth, bool incremental, bool rep, bool owner_filter) {
+    const int L = (int)sh.size();
+    std::vector<ListedTerminal> all;
+    std::vector<int> all_shard;
+    for (int l = 0; l < (rep ? 1 : L); l++) {
+      Shard& S = sh[l];
+      uint64_t F = 0;
+      for (uint64_t c : S.seg_cnt) F += c;
+      if (!F) continue;
+      std::vector<ListedTerminal> recs;
+      uint64_t count = 0, full = 0;
+      const uint64_t cap = std::max<uint64_t>(S.lc.n_terminals, 64);
+      DSL_TRY(list_pass(S, succ_depth, incremental, owner_filter, cap, recs, &count, &full));
+      if (count > cap || full) {  // once more, at the exact size (every unresolved candidate may be distinct)
+        const uint64_t cap2 = count + full;
+        if (getenv("DSL_LEVEL_TRACE"))
+          fprintf(stderr, "[terminals] shard %d: %llu listed (+%llu unresolved) past the room for %llu: second pass\n",
+                  S.gid, (unsigned long long)count, (unsigned long long)full, (unsigned long long)cap);
+        DSL_TRY(list_pass(S, succ_depth, incremental, owner_filter, cap2, recs, &count, &full));
+        if (count > cap2 || full) {
+          set_error("terminal list: the pass overflowed at its exact size");
+          return DSL_ERR_ARG;
+        }
+      }
+      // the scratch table's work: no state twice in one shard's list
+      std::vector<ListedTerminal> chk(recs);
+      std::sort(chk.begin(), chk.end(), listed_less);
+      for (size_t i = 1; i < chk.size(); i++)
+        if (chk[i].rec.verdict != V_TERM_EXCEPTION && chk[i].rec.verdict == chk[i - 1].rec.verdict &&
+            chk[i].fp.hi == chk[i - 1].fp.hi && chk[i].fp.lo == chk[i - 1].fp.lo) {
+          set_error("terminal list: a state was listed twice by one shard");
+          return DSL_ERR_ARG;
+        }
+      for (auto& r : recs) {
+        r.rec.parent |= (uint64_t)S.gid << 48;
+        all.push_back(r);
+      }
+    }
+    // two shards' parents can reach the same state: one entry per fingerprint (never an exception)
+    std::stable_sort(all.begin(), all.end(), listed_less);
+    size_t m = 0;
+    for (size_t i = 0; i < all.size(); i++) {
+      if (m && all[i].rec.verdict != V_TERM_EXCEPTION && all[i].rec.verdict == all[m - 1].rec.verdict &&
+          all[i].fp.hi == all[m - 1].fp.hi && all[i].fp.lo == all[m - 1].fp.lo)
+        continue;
+      all[m++] = all[i];
+    }
+    all.resize(m);
+    term_total = m;
+    const size_t n = std::min<size_t>(m, (size_t)hset.max_terminals);
+    if (getenv("DSL_LEVEL_TRACE"))
+      fprintf(stderr, "[terminals] depth %d: %zu terminals, %zu kept\n", succ_depth, m, n);
+    term_list.assign(n, ListedTrace{});
+    for (size_t i = 0; i < n; i++) {
+      term_list[i].verdict = all[i].rec.verdict;
+      term_list[i].pred_index = all[i].rec.verdict == V_TERM_EXCEPTION ? -1 : all[i].rec.pred_index;
+      term_list[i].events.push_back(all[i].rec.event);
+    }
+    // the chains, one history level at a time for all kept terminals
+    const int nlev = (int)sh[0].level_size.size();
+    if (!n || nlev < 3) return DSL_OK;
+    DevBufs bufs;
+    uint64_t* ref[2] = {nullptr, nullptr};
+    DSL_TRY(bufs.get(&ref[0], n * 16));
+    DSL_TRY(bufs.get(&ref[1], n * 16));
+    std::vector<uint64_t> hops((size_t)(nlev - 1) * n * 2);  // [0, 2n): the terminals' parents, then one block per level
+    for (size_t i = 0; i < n; i++) {
+      hops[2 * i] = all[i].rec.parent;
+      hops[2 * i + 1] = all[i].rec.event;
+    }
+    DSL_HIP(hipMemcpyAsync(ref[0], hops.data(), n * 16, hipMemcpyHostToDevice, stream));
+    int cur = 0, blk = 1;
+    for (int lev = nlev - 2; lev >= 1; lev--, blk++) {
+      DSL_HIP(hipMemsetAsync(ref[cur ^ 1], 0xff, n * 16, stream));  // an entry no shard answers stays ~0
+      for (int l = 0; l < L; l++) {
+        Shard& S = sh[l];
+        if ((size_t)lev >= S.hpar.size() || !S.hpar[lev]) continue;
+        hipLaunchKernelGGL(k_hist_gather, dim3((unsigned)((n + kBlock - 1) / kBlock)), dim3(kBlock), 0, stream,
+                           (const uint64_t*)S.hpar[lev], (const uint32_t*)S.hev[lev], S.hcap[lev], S.gid,
+                           (const uint64_t*)ref[cur], ref[cur ^ 1], (uint64_t)n);
+        DSL_HIP(hipGetLastError());
+      }
+      cur ^= 1;
+      DSL_HIP(hipMemcpyAsync(hops.data() + (size_t)blk * n * 2, ref[cur], n * 16, hipMemcpyDeviceToHost, stream));
+    }
+    DSL_TRY(hsync());
+    for (int b = 1; b < blk; b++)
+      for (size_t i = 0; i < n; i++) {
+        const uint64_t* h = hops.data() + ((size_t)b * n + i) * 2;
+        if (h[0] == ~0ull) {
+          set_error("terminal list: a parent chain left the history");
+          return DSL_ERR_ARG;
+        }
+        term_list[i].events.push_back((uint32_t)h[1]);
+      }
+    for (auto& t : term_list) std::reverse(t.events.begin(), t.events.end());
+    return DSL_OK;
+  }
+
   // ---- sharded levels: the fast path ----------------------------------------------
   // A sharded level moves its routed fingerprints in fixed-size SLABS: per (source, owner) pair
   // one region of kRouteSegs sub-slabs of `cs` records plus a header with their counts
@@ -1412,6 +1602,13 @@ struct BfsEngine : EngineBase {
   uint64_t restart_buckets = 0;
   std::chrono::steady_clock::time_point t_run0;
   int run(dsl_result** out) override {
+    // the terminal lists of several processes are not gathered: refused before any collective
+    // (every rank carries the same settings, so every rank refuses alike)
+    if (hset.max_terminals > 0 && comm && W > 1) {
+      set_error("max_terminals > 0 is not supported in a search over more than one process (world_size " +
+                std::to_string(W) + "): run it in one process (virtual shards are supported)");
+      return DSL_ERR_ARG;
+    }
     restart_buckets = 0;
     t_run0 = std::chrono::steady_clock::now();
     for (int attempt = 0;; attempt++) {
@@ -1453,6 +1650,8 @@ struct BfsEngine : EngineBase {
     stats = dsl_stats{};
     stats.state_bytes = NW * 4;
     stats.world_size = W;
+    term_list.clear();
+    term_total = 0;
     if (!have_init) {
       uint8_t tmp[sizeof(init)];
       DSL_TRY(get_initial(tmp, sizeof(init)));
@@ -2008,6 +2207,7 @@ struct BfsEngine : EngineBase {
             DSL_TRY(comm->allreduce_u64(&enc, 1, true, stream));
           }
         }
+        const bool owner_filtered = route && first_sharded;  // this level expanded only the parents each shard owns
         if (route) first_sharded = false;
         if (gsum[3]) {
           set_error("a successor exceeded the packed state's bounds (" + std::to_string(gsum[3]) + " times)");
@@ -2116,6 +2316,9 @@ struct BfsEngine : EngineBase {
           }
           std::reverse(evs.begin(), evs.end());
           trace_events = evs;
+          // every terminal of this level (a level the deadline cut short is not enumerated)
+          if (hset.max_terminals > 0 && !level_tup)
+            DSL_TRY(list_terminals(depth, depth - 1 > init_depth, rep, owner_filtered));
           break;
         }
         if (hset.do_checks != DSL_CHECKS_NONE)
@@ -2210,6 +2413,36 @@ struct BfsEngine : EngineBase {
       }
       r->terminal_state = (uint8_t*)malloc(sizeof(init));
       std::memcpy(r->terminal_state, &s, sizeof(init));
+      if (hset.max_terminals > 0) {
+        // a terminal initial state, or a level the deadline cut short: the reported terminal alone
+        if (term_list.empty()) {
+          term_list.push_back(ListedTrace{end == DSL_EXCEPTION_THROWN ? V_TERM_EXCEPTION
+                                          : end == DSL_INVARIANT_VIOLATED ? V_TERM_INVARIANT : V_TERM_GOAL,
+                                          pred_index, trace_events});
+          term_total = 1;
+        }
+        r->terminals_total = term_total;
+        r->n_terminals = (int32_t)term_list.size();
+        r->terminals = (dsl_terminal*)calloc(term_list.size(), sizeof(dsl_terminal));
+        for (size_t t = 0; t < term_list.size(); t++) {
+          const ListedTrace& lt = term_list[t];
+          dsl_terminal& o = r->terminals[t];
+          o.end_condition = lt.verdict == V_TERM_EXCEPTION ? DSL_EXCEPTION_THROWN
+                            : lt.verdict == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED : DSL_GOAL_FOUND;
+          o.predicate_index = lt.pred_index;
+          o.trace_len = (int32_t)lt.events.size();
+          o.trace = (dsl_event*)calloc(lt.events.size() + 1, sizeof(dsl_event));
+          typename P::State ts = init, tn;
+          for (size_t i = 0; i < lt.events.size(); i++) {
+            describe_event<P>(ts.w, (int)lt.events[i], prm, dset, &o.trace[i]);
+            full_step<P>(ts.w, (int)lt.events[i], tn.w, prm, dset);
+            ts = tn;
+          }
+          o.state = (uint8_t*)malloc(sizeof(init));
+          std::memcpy(o.state, &ts, sizeof(init));
+        }
+        term_list.clear();
+      }
       trace_events.clear();
     }
     if (trace_levels)

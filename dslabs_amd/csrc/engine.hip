@@ -532,6 +532,11 @@ void dsl_result_free(dsl_result* r) {
   free(r->per_depth);
   free(r->trace);
   free(r->terminal_state);
+  for (int32_t i = 0; i < r->n_terminals; i++) {
+    free(r->terminals[i].trace);
+    free(r->terminals[i].state);
+  }
+  free(r->terminals);
   free(r);
 }
 

@@ -1970,6 +1970,163 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
   block_flush(s_red, &a.ctr->next_work, c_next_work);
 }
 
+// ---- every terminal of the level that ended the search (dsl_settings.max_terminals) ---------------
+// Runs once, after the terminal level, over that level's frontier (still in `cur`): the level's
+// expansion again with every successor taken as new, as the find mode of k_level does -- a
+// successor first seen at an earlier level was judged there and is not terminal (checkState is a
+// function of the state), so the visited table is neither read nor written. A kernel of its own:
+// k_level's register allocation must not move for a pass that runs once per search.
+// A wave stages up to mat_per_max parents (contiguous rows of one segment) in LDS, counts their
+// enabled events, and runs one lane per (parent, event): delta_step, the successor's fingerprint
+// from the parent's, judge_view with the level's depth and `incremental` flag. A TERMINAL state is
+// listed once: the first lane to insert its fingerprint into the pass's own scratch table (fresh
+// and empty, one CAS per probe) wins; an exceptional successor equals no other and skips the
+// table (its fingerprint: exception_key, as in k_level). A winner reserves its slot with one
+// returning atomic per wavefront; the counter runs past the list's room (the host then runs the
+// pass again at the exact size).
+struct ListedTerminal {
+  TerminalRec rec;  // key: term_key of fp.hi
+  Fp fp;            // the state's full fingerprint (an exceptional successor: {exception_key, parent's lo + event + 1})
+};
+
+template <class P>
+struct ListArgs {
+  const uint32_t* cur;
+  const Fp* cur_fp;
+  SegTable segs;             // row ranges of the frontier; pb = parents per wave chunk, chunk0 in those chunks
+  int32_t me, W;
+  int32_t owner_filter;      // the first sharded level: only the parents this shard owns were expanded
+  int32_t depth, incremental;
+  Table scratch;
+  ListedTerminal* out;
+  uint64_t cap;
+  unsigned long long* ctr;   // [0]: terminals listed (past cap: not written), [1]: probes that found the table full
+};
+
+template <class P>
+__global__ void __launch_bounds__(kBlock) k_list_terminals(ListArgs<P> a, typename P::Params prm, DevSettings set) {
+  constexpr int NW = Layout<P>::kWords;
+  constexpr int PMAX = mat_per_max<P>();
+  constexpr int NWV = kBlock / 64;
+  __shared__ uint32_t s_nodew[kBlock * P::kNodeWords];
+  __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kBlock * P::kMaxSends : 1];
+  __shared__ int s_off[NWV][PMAX + 1];
+  extern __shared__ __align__(16) uint32_t s_mrows[];  // NWV x PMAX parent rows
+  const int lane = __lane_id(), wid = threadIdx.x >> 6;
+  uint32_t* wrows = s_mrows + wid * PMAX * NW;
+  int* off = s_off[wid];
+  const int per = a.segs.pb;  // <= PMAX (host)
+  const uint64_t nchunks = a.segs.chunk0[a.segs.n];
+  for (uint64_t c = (uint64_t)blockIdx.x * NWV + wid; c < nchunks; c += (uint64_t)gridDim.x * NWV) {
+    int q = 0;
+    while (q + 1 < a.segs.n && c >= a.segs.chunk0[q + 1]) q++;
+    const uint64_t r0 = (c - a.segs.chunk0[q]) * (uint64_t)per;
+    const uint64_t p0 = a.segs.base[q] + r0;
+    const int nr = (int)min<uint64_t>((uint64_t)per, a.segs.cnt[q] - r0);
+    // the chunk's rows (contiguous) into LDS with LDS-DMA, 64 16-byte units per wave-instruction
+    const int n16 = nr * (NW / 4);
+    const uint4* src = reinterpret_cast<const uint4*>(a.cur + p0 * NW);
+    for (int b = 0; b < n16; b += 64)
+      if (b + lane < n16)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + b + lane),
+                                         (__attribute__((address_space(3))) void*)(wrows + 4 * b), 16, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // enabled events per parent, and their exclusive scan
+    int x = 0;
+    if (lane < nr && !(a.owner_filter && owner_of(a.cur_fp[p0 + lane], a.W) != a.me))
+      x = count_events<P>(wrows + lane * NW, prm, set);
+    x = (int)wave_incl_sum((uint32_t)x);
+    const int total = (int)rl32((uint32_t)x, 63);
+    if (lane < nr) off[lane + 1] = x;
+    if (lane == 0) off[0] = 0;
+    __builtin_amdgcn_wave_barrier();
+    for (int t0 = 0; t0 < total; t0 += 64) {
+      const int t = t0 + lane;
+      const bool live = t < total;
+      bool cand = false, exc = false;
+      int tv = 0, tpi = -1, k = 0, j = 0;
+      Fp f{0, 0};
+      if (live) {
+        // the parent of item t: the last j with off[j] <= t
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (off[mid] <= t) lo = mid;
+          else hi = mid - 1;
+        }
+        j = lo;
+        k = t - off[j];
+        const uint32_t* w = wrows + j * NW;
+        const Fp pf = a.cur_fp[p0 + j];
+        Delta<P> d;
+        d.node = 0;
+        d.out.n = 0;
+        d.keep = 0;
+        const int rc = delta_step<P>(w, k, d, prm, set);
+        if (rc == STEP_OK) {
+          const int dn = delta_new_count<P>(d);
+          // a successor that changes neither its node nor the network is its parent, which was
+          // expanded: not terminal (the events the no-op filter proves idle are among these)
+          const bool noop = dn == 0 && same_words<P::kNodeWords>(d.nw, w + d.node * P::kNodeWords);
+          if (!noop) {
+            f = delta_fingerprint<P>(w, pf, d);
+            int pi = -1;
+            uint32_t* my_nw = s_nodew + threadIdx.x * P::kNodeWords;
+#pragma unroll
+            for (int i = 0; i < P::kNodeWords; i++) my_nw[i] = d.nw[i];
+            NodeView view{w, P::kNodeWords, d.node, my_nw};
+            if constexpr (NetPreds<P>::value) {
+              typename P::Rec* ms = s_sends + threadIdx.x * P::kMaxSends;
+              int n = 0;
+#pragma unroll
+              for (int i = 0; i < P::kMaxSends; i++)
+                if ((d.keep >> i) & 1u) ms[n++] = d.out.r[i];
+              view.sends = ms;
+              view.nsends = n;
+            }
+            const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
+            if (v >= V_TERM_EXCEPTION) {
+              cand = true;
+              tv = v;
+              tpi = pi;
+            }
+          }
+        } else if (rc == STEP_EXCEPTION) {
+          cand = exc = true;
+          tv = V_TERM_EXCEPTION;
+          f = Fp{exception_key(pf, k), pf.lo + (uint64_t)k + 1ull};
+        }  // STEP_OVERFLOW: the level reported it
+      }
+      bool win = exc;
+      if (cand && !exc) {
+        const int ins = table_insert(a.scratch, f);
+        win = ins == INS_NEW;
+        if (ins == INS_FULL) atomicAdd(&a.ctr[1], 1ull);
+      }
+      const unsigned long long slot = wave_reserve(&a.ctr[0], win);
+      if (win && slot < a.cap)
+        a.out[slot] = ListedTerminal{TerminalRec{tv, tpi, (uint32_t)k, 0u, p0 + (uint64_t)j, term_key(tv, f.hi)}, f};
+    }
+    __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
+  }
+}
+
+// One hop of many parent chains at once: entry i of `in` holds a row reference (shard << 48 | row)
+// into history level `lev`; this shard answers its own rows with that row's {parent reference,
+// event} in `out` (the next hop's `in`), and leaves the others' entries to their shards' launches.
+__global__ void __launch_bounds__(kBlock) k_hist_gather(const uint64_t* hpar, const uint32_t* hev, uint64_t rows,
+                                                        int me, const uint64_t* in, uint64_t* out, uint64_t n) {
+  const uint64_t i = (uint64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (i >= n) return;
+  const uint64_t ref = in[2 * i];
+  if ((int)(ref >> 48) != me) return;
+  const uint64_t idx = ref & ((1ull << 48) - 1);
+  const bool ok = idx < rows;
+  out[2 * i] = ok ? hpar[idx] : ~0ull;  // ~0: a reference past the level's rows (the host fails the search)
+  out[2 * i + 1] = ok ? (uint64_t)hev[idx] : 0ull;
+}
+
 }  // namespace dsl
 
 namespace dsl {

@@ -150,6 +150,17 @@ class SearchSettings:
         # stepped twice (idempotence); counts in SearchResults.checks
         self.do_checks = _lib.DSL_CHECKS_NONE
         self.check_sample = 0
+        # dsl_settings.max_terminals: every terminal state of the level that ends a BFS, at most
+        # this many listed (SearchResults.terminals()); 0 = only the reported one
+        self.max_terminals = 0
+
+    def maxTerminals(self, n: int) -> "SearchSettings":
+        """List every terminal state of the level that ends a BFS (all shortest counterexamples,
+        all goal states of a staged search), at most ``n`` of them; 0 turns the list off."""
+        if n < 0:
+            raise ValueError("maxTerminals: n must be >= 0")
+        self.max_terminals = int(n)
+        return self
 
     def doErrorChecks(self, on: bool = True) -> "SearchSettings":
         self.do_checks = _lib.DSL_CHECKS_ERRORS if on else _lib.DSL_CHECKS_NONE
@@ -273,7 +284,7 @@ class SearchSettings:
                 tuple(self._link.items()), tuple(self._sender.items()), tuple(self._receiver.items()),
                 tuple(self._timers_active.items()), tuple(self._invariants), tuple(self._goals), tuple(self._prunes),
                 self.table_log2_slots, self.max_frontier_states, self.memory_budget_bytes, self.do_checks,
-                self.check_sample)
+                self.check_sample, self.max_terminals)
 
     def _encode(self, state: "SearchState") -> _lib.dsl_settings:
         """The C ABI form (dsl_settings); the same object again while nothing it reads changed,
@@ -323,6 +334,7 @@ class SearchSettings:
         s.memory_budget_bytes = self.memory_budget_bytes
         s.do_checks = self.do_checks
         s.check_sample = self.check_sample
+        s.max_terminals = self.max_terminals
         return s
 
 
@@ -427,6 +439,8 @@ class SearchResults:
         self.successors = successors
         self.checks = {"run": 0, "not_deterministic": 0, "not_idempotent": 0, "first_not_deterministic": None,
                        "first_not_idempotent": None}
+        self._terminals: list = []
+        self._terminals_total = 0
 
     def endCondition(self) -> EndCondition:
         return self._end
@@ -453,6 +467,29 @@ class SearchResults:
 
     def exceptionThrown(self) -> bool:
         return self._end == EndCondition.EXCEPTION_THROWN
+
+    # every terminal of the level that ended a BFS (SearchSettings.maxTerminals) ----------------
+    def terminals(self) -> list:
+        """``(EndCondition, PredicateResult | None, SearchState)`` of every listed terminal state, in
+        the engine's order: exceptions, then invariant violations, then goals, each by fingerprint;
+        the first entry is the terminal the search reports. Empty unless maxTerminals(n > 0)."""
+        return list(self._terminals)
+
+    def numTerminals(self) -> int:
+        """All terminal states of that level, also those past the maxTerminals cap."""
+        return self._terminals_total
+
+    def _terminals_of(self, end: EndCondition) -> List[SearchState]:
+        return [s for e, _, s in self._terminals if e == end]
+
+    def invariantViolatingStates(self) -> List[SearchState]:
+        return self._terminals_of(EndCondition.INVARIANT_VIOLATED)
+
+    def goalMatchingStates(self) -> List[SearchState]:
+        return self._terminals_of(EndCondition.GOAL_FOUND)
+
+    def exceptionalStates(self) -> List[SearchState]:
+        return self._terminals_of(EndCondition.EXCEPTION_THROWN)
 
     def statesPerSecond(self) -> float:
         return self.states / self.elapsed_s if self.elapsed_s > 0 else float("inf")
@@ -621,6 +658,22 @@ class Engine:
             res = SearchResults(end, r.states, per_depth, r.initial_depth, r.max_depth, terminal, pred,
                                 r.elapsed_s, r.successors)
             res._last = last
+            res._terminals_total = r.terminals_total
+            base = state.trace() if state.packed is not None else []
+            for i in range(r.n_terminals):
+                t = r.terminals[i]
+                t_end = EndCondition(t.end_condition)
+                t_raw = [t.trace[j] for j in range(t.trace_len)]
+                t_state = SearchState(
+                    self.protocol, bytes(ctypes.cast(t.state, ctypes.POINTER(ctypes.c_uint8 * r.state_bytes)).contents),
+                    r.terminal_depth, base + [self.protocol.render_event(e) for e in t_raw],
+                    [_lib.dsl_event.from_buffer_copy(e) for e in t_raw], state._dropped)
+                t_pred = None
+                if t_end == EndCondition.INVARIANT_VIOLATED:
+                    t_pred = PredicateResult(settings.invariants()[t.predicate_index], False)
+                elif t_end == EndCondition.GOAL_FOUND:
+                    t_pred = PredicateResult(settings.goals()[t.predicate_index], True)
+                res._terminals.append((t_end, t_pred, t_state))
             # CheckLogger.notDeterministic / notIdempotent (T/utils/CheckLogger.java:104-121)
             res.checks = {"run": r.checks_run, "not_deterministic": r.not_deterministic,
                           "not_idempotent": r.not_idempotent,

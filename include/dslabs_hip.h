@@ -34,11 +34,13 @@
 extern "C" {
 #endif
 
-#define DSL_ABI_VERSION 5 /* 2: dsl_set_dropped; dsl_stats host_syncs / table_rehashes / rccl_version;
+#define DSL_ABI_VERSION 6 /* 2: dsl_set_dropped; dsl_stats host_syncs / table_rehashes / rccl_version;
                             3: dsl_engine_config.flags, dsl_host_comm.flags;
                             4: dsl_settings.do_checks / check_sample, dsl_result check counts,
                                dsl_stats exchange_rounds / fast_levels / completions;
-                            5: dsl_stats deduped */
+                            5: dsl_stats deduped;
+                            6: dsl_settings.max_terminals, dsl_result terminals_total / n_terminals /
+                               terminals, dsl_terminal */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -164,6 +166,10 @@ typedef struct {
      successor (idempotence, not necessarily an error). Counts in dsl_result. */
   int32_t do_checks;        /* DSL_CHECKS_* */
   int32_t check_sample;
+  /* Every terminal state of the level that ends a BFS (dsl_result.terminals), at most this many
+     listed; 0 = off: only the one reported terminal, as before ABI 6. Read by dsl_run alone. */
+  int32_t max_terminals;
+  int32_t reserved;
 } dsl_settings;
 
 /* dsl_settings.do_checks */
@@ -198,6 +204,16 @@ typedef struct {
   int64_t fields[DSL_MAX_EVENT_FIELDS];
 } dsl_event;
 
+/* One terminal state of the level that ended a BFS (dsl_result.terminals). */
+typedef struct {
+  int32_t end_condition;    /* DSL_EXCEPTION_THROWN, DSL_INVARIANT_VIOLATED or DSL_GOAL_FOUND */
+  int32_t predicate_index;  /* index in invariants[] / goals[] that fired first, -1 for an exception */
+  int32_t trace_len;        /* terminal_depth - initial_depth */
+  int32_t reserved;
+  dsl_event* trace;         /* [trace_len]: events from the initial state to this terminal */
+  uint8_t* state;           /* packed state (dsl_result.state_bytes), the trace replayed on the host */
+} dsl_terminal;
+
 typedef struct {
   int32_t end_condition;    /* dsl_end_condition */
   int32_t terminal_depth;   /* depth of the reported terminal state, -1 if none */
@@ -224,6 +240,28 @@ typedef struct {
   uint64_t not_idempotent;
   dsl_event first_not_deterministic;
   dsl_event first_not_idempotent;
+  /* dsl_settings.max_terminals > 0 and a dsl_run that ended EXCEPTION_THROWN, INVARIANT_VIOLATED or
+     GOAL_FOUND: every terminal of the level that ended the search. BFS finishes that level
+     (Search.java:370-385 keeps the best of it by priority), and this is the whole set: every
+     distinct state first discovered at terminal_depth that checkState judges TERMINAL
+     (Search.java:468-504), listed once however many (parent, event) pairs reach it, and every
+     exceptional successor generated at that level, one per (parent, event) and never merged (a
+     Throwable equals only itself). A terminal initial state is the whole list.
+     Order: ascending by priority (EXCEPTION, INVARIANT, GOAL), then by the state's 128-bit
+     fingerprint, so terminals[0] is the terminal reported above (same state, end condition and
+     predicate index) and the listed states never depend on arrival order or on sharding; a trace
+     is A shortest trace (a state with two parents may be recorded through either).
+     terminals_total is the whole count; the list holds the first min(terminals_total,
+     max_terminals) of that order, and only those have a trace and a state.
+     A level cut short by max_time_ms is not enumerated: the list is the reported terminal alone
+     and terminals_total = 1. Any other result (and dsl_run_dfs, dsl_replay,
+     dsl_human_readable_trace): terminals_total = 0, n_terminals = 0, terminals = NULL.
+     A search over more than one process (world_size > 1) with max_terminals > 0 is refused with
+     DSL_ERR_ARG; virtual shards in one process are supported. */
+  uint64_t terminals_total;
+  int32_t n_terminals;
+  int32_t reserved;
+  dsl_terminal* terminals;  /* [n_terminals] */
 } dsl_result;
 
 typedef struct dsl_engine dsl_engine;

@@ -171,10 +171,22 @@ public final class GpuBFS {
     };
     res.endCondition(end);
     if (r.terminalDepth() < 0) return res;
-    // the terminal on the Java handlers: each device event is the unique matching event of the
-    // state it meets (events(settings), SearchState.java:226-252)
+    SearchState s = rebuild(init, settings, desc, r.trace());
+    switch (end) {
+      case EXCEPTION_THROWN -> res.exceptionThrown(s);
+      case INVARIANT_VIOLATED -> res.invariantViolated(s, fired(settings.invariants(), r.predicateIndex(), s, true));
+      case GOAL_FOUND -> res.goalFound(s, fired(settings.goals(), r.predicateIndex(), s, false));
+      default -> {}
+    }
+    return res;
+  }
+
+  // A device trace on the Java handlers: each device event is the unique matching event of the
+  // state it meets (events(settings), SearchState.java:226-252).
+  private static SearchState rebuild(SearchState init, SearchSettings settings, GpuProtocols.Desc desc,
+                                     Dsl.Event[] trace) {
     SearchState s = init;
-    for (Dsl.Event de : r.trace()) {
+    for (Dsl.Event de : trace) {
       Event match = null;
       for (Event je : s.events(settings))
         if (desc.matches(je, de)) {
@@ -184,13 +196,31 @@ public final class GpuBFS {
       if (match == null) throw new IllegalStateException("device trace event has no Java counterpart: " + de);
       s = s.stepEvent(match, settings, false);
     }
-    switch (end) {
-      case EXCEPTION_THROWN -> res.exceptionThrown(s);
-      case INVARIANT_VIOLATED -> res.invariantViolated(s, fired(settings.invariants(), r.predicateIndex(), s, true));
-      case GOAL_FOUND -> res.goalFound(s, fired(settings.goals(), r.predicateIndex(), s, false));
-      default -> {}
+    return s;
+  }
+
+  /** One terminal state of the level that ended a BFS, rebuilt on the Java handlers. */
+  public record Terminal(EndCondition endCondition, PredicateResult predicate, SearchState state) {}
+
+  /**
+   * Every terminal of the level that ended the search (dsl_result.terminals: all shortest
+   * counterexamples, all goal states of a staged search), in the engine's order -- exceptions, then
+   * invariant violations, then goals, each by fingerprint; the first is the terminal the search
+   * reports. Empty unless the settings were encoded with max_terminals > 0 (Dsl.OFF_MAX_TERMINALS).
+   * Each state is replayed like the single terminal (results), its predicate re-tested on it.
+   */
+  static List<Terminal> terminals(SearchState init, SearchSettings settings, GpuProtocols.Desc desc, Dsl.Result r) {
+    List<Terminal> out = new ArrayList<>();
+    for (Dsl.Terminal t : r.terminals()) {
+      SearchState s = rebuild(init, settings, desc, t.trace());
+      switch (t.endCondition()) {
+        case Dsl.END_EXCEPTION_THROWN -> out.add(new Terminal(EndCondition.EXCEPTION_THROWN, null, s));
+        case Dsl.END_INVARIANT_VIOLATED -> out.add(new Terminal(EndCondition.INVARIANT_VIOLATED,
+            fired(settings.invariants(), t.predicateIndex(), s, true), s));
+        default -> out.add(new Terminal(EndCondition.GOAL_FOUND, fired(settings.goals(), t.predicateIndex(), s, false), s));
+      }
     }
-    return res;
+    return out;
   }
 
   // The predicate the device reported, re-tested on the Java state for its result and detail.

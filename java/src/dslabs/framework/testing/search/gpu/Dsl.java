@@ -24,12 +24,12 @@ public final class Dsl {
   public static final long SIZE_PREDICATE = 24, OFF_PRED_ID = 0, OFF_PRED_NEGATE = 4, OFF_PRED_ARG0 = 8,
       OFF_PRED_ARG1 = 16;
   // dsl_settings
-  public static final long SIZE_SETTINGS = 3488, OFF_MAX_DEPTH = 0, OFF_MAX_TIME_MS = 4, OFF_NETWORK_ACTIVE = 8,
+  public static final long SIZE_SETTINGS = 3496, OFF_MAX_DEPTH = 0, OFF_MAX_TIME_MS = 4, OFF_NETWORK_ACTIVE = 8,
       OFF_DELIVER_TIMERS = 12, OFF_LINK_ACTIVE = 16, OFF_SENDER_ACTIVE = 1040, OFF_RECEIVER_ACTIVE = 1072,
       OFF_TIMERS_ACTIVE = 1104, OFF_N_INVARIANTS = 1136, OFF_N_GOALS = 1140, OFF_N_PRUNES = 1144,
       OFF_INVARIANTS = 1152, OFF_GOALS = 1536, OFF_PRUNES = 1920, OFF_TABLE_LOG2 = 2304, OFF_N_POOL = 2308,
       OFF_MAX_FRONTIER = 2312, OFF_MEMORY_BUDGET = 2320, OFF_POOL = 2328, OFF_DO_CHECKS = 3480,
-      OFF_CHECK_SAMPLE = 3484;
+      OFF_CHECK_SAMPLE = 3484, OFF_MAX_TERMINALS = 3488;
   public static final int CHECKS_NONE = 0, CHECKS_ERRORS = 1, CHECKS_ALL = 2;
   public static final int MAX_NODES = 32, MAX_PREDICATES = 16, MAX_POOL = 48;
   // dsl_engine_config
@@ -39,14 +39,18 @@ public final class Dsl {
   public static final long SIZE_EVENT = 96, OFF_EV_IS_TIMER = 0, OFF_EV_FROM = 4, OFF_EV_TO = 8, OFF_EV_TYPE = 12,
       OFF_EV_N_FIELDS = 16, OFF_EV_TIMER_MIN = 20, OFF_EV_TIMER_MAX = 24, OFF_EV_FIELDS = 32;
   // dsl_result
-  public static final long SIZE_RESULT = 320, OFF_RES_END = 0, OFF_RES_TERMINAL_DEPTH = 4, OFF_RES_PRED_INDEX = 8,
+  public static final long SIZE_RESULT = 344, OFF_RES_END = 0, OFF_RES_TERMINAL_DEPTH = 4, OFF_RES_PRED_INDEX = 8,
       OFF_RES_MAX_DEPTH = 12, OFF_RES_STATES = 16, OFF_RES_N_LEVELS = 24, OFF_RES_TRACE_LEN = 28,
       OFF_RES_PER_DEPTH = 32, OFF_RES_TRACE = 40, OFF_RES_TERMINAL_STATE = 48, OFF_RES_STATE_BYTES = 56,
       OFF_RES_INITIAL_DEPTH = 60, OFF_RES_ELAPSED = 64, OFF_RES_CHECKS_RUN = 104, OFF_RES_NOT_DETERMINISTIC = 112,
-      OFF_RES_NOT_IDEMPOTENT = 120, OFF_RES_FIRST_NOT_DETERMINISTIC = 128, OFF_RES_FIRST_NOT_IDEMPOTENT = 224;
+      OFF_RES_NOT_IDEMPOTENT = 120, OFF_RES_FIRST_NOT_DETERMINISTIC = 128, OFF_RES_FIRST_NOT_IDEMPOTENT = 224,
+      OFF_RES_TERMINALS_TOTAL = 320, OFF_RES_N_TERMINALS = 328, OFF_RES_TERMINALS = 336;
+  // dsl_terminal: one terminal state of the level that ended a BFS (dsl_settings.max_terminals)
+  public static final long SIZE_TERMINAL = 32, OFF_TERM_END = 0, OFF_TERM_PRED_INDEX = 4, OFF_TERM_TRACE_LEN = 8,
+      OFF_TERM_TRACE = 16, OFF_TERM_STATE = 24;
 
   // DSL_ABI_VERSION: the struct layout above; a library of another version is refused
-  public static final int ABI_VERSION = 5;
+  public static final int ABI_VERSION = 6;
   public static final int MAX_EVENT_FIELDS = 8;
 
   // dsl_protocol_id (include/dslabs_hip.h)
@@ -302,10 +306,23 @@ public final class Dsl {
     }
   }
 
+  /** dsl_terminal, copied: a listed terminal's end condition, predicate index, trace and packed state. */
+  public record Terminal(int endCondition, int predicateIndex, Event[] trace, byte[] state) {
+    static Terminal at(MemorySegment t, int stateBytes) {
+      int tl = t.get(ValueLayout.JAVA_INT, OFF_TERM_TRACE_LEN);
+      Event[] tr = new Event[tl];
+      MemorySegment tp = t.get(A, OFF_TERM_TRACE).reinterpret(SIZE_EVENT * Math.max(1, tl));
+      for (int i = 0; i < tl; i++) tr[i] = Event.at(tp.asSlice(SIZE_EVENT * i, SIZE_EVENT));
+      return new Terminal(t.get(ValueLayout.JAVA_INT, OFF_TERM_END), t.get(ValueLayout.JAVA_INT, OFF_TERM_PRED_INDEX), tr,
+          t.get(A, OFF_TERM_STATE).reinterpret(stateBytes).toArray(ValueLayout.JAVA_BYTE));
+    }
+  }
+
   /** dsl_result, copied. */
   public record Result(int endCondition, int terminalDepth, int predicateIndex, int maxDepth, long states,
                        long[] perDepth, Event[] trace, byte[] terminalState, int initialDepth, double elapsedSecs,
-                       long checksRun, long notDeterministic, long notIdempotent) {
+                       long checksRun, long notDeterministic, long notIdempotent, long terminalsTotal,
+                       Terminal[] terminals) {
     static Result copyOf(MemorySegment r) {
       int nl = r.get(ValueLayout.JAVA_INT, OFF_RES_N_LEVELS), tl = r.get(ValueLayout.JAVA_INT, OFF_RES_TRACE_LEN);
       long[] pd = new long[nl];
@@ -318,11 +335,20 @@ public final class Dsl {
       byte[] st = null;
       if (!sp.equals(MemorySegment.NULL))
         st = sp.reinterpret(r.get(ValueLayout.JAVA_INT, OFF_RES_STATE_BYTES)).toArray(ValueLayout.JAVA_BYTE);
+      // every terminal of the level that ended the search (empty unless max_terminals > 0)
+      int nt = r.get(ValueLayout.JAVA_INT, OFF_RES_N_TERMINALS);
+      Terminal[] terms = new Terminal[nt];
+      if (nt > 0) {
+        MemorySegment ts = r.get(A, OFF_RES_TERMINALS).reinterpret(SIZE_TERMINAL * nt);
+        for (int i = 0; i < nt; i++)
+          terms[i] = Terminal.at(ts.asSlice(SIZE_TERMINAL * i, SIZE_TERMINAL), r.get(ValueLayout.JAVA_INT, OFF_RES_STATE_BYTES));
+      }
       return new Result(r.get(ValueLayout.JAVA_INT, OFF_RES_END), r.get(ValueLayout.JAVA_INT, OFF_RES_TERMINAL_DEPTH),
           r.get(ValueLayout.JAVA_INT, OFF_RES_PRED_INDEX), r.get(ValueLayout.JAVA_INT, OFF_RES_MAX_DEPTH),
           r.get(ValueLayout.JAVA_LONG, OFF_RES_STATES), pd, tr, st, r.get(ValueLayout.JAVA_INT, OFF_RES_INITIAL_DEPTH),
           r.get(ValueLayout.JAVA_DOUBLE, OFF_RES_ELAPSED), r.get(ValueLayout.JAVA_LONG, OFF_RES_CHECKS_RUN),
-          r.get(ValueLayout.JAVA_LONG, OFF_RES_NOT_DETERMINISTIC), r.get(ValueLayout.JAVA_LONG, OFF_RES_NOT_IDEMPOTENT));
+          r.get(ValueLayout.JAVA_LONG, OFF_RES_NOT_DETERMINISTIC), r.get(ValueLayout.JAVA_LONG, OFF_RES_NOT_IDEMPOTENT),
+          r.get(ValueLayout.JAVA_LONG, OFF_RES_TERMINALS_TOTAL), terms);
     }
   }
 }

@@ -77,6 +77,9 @@ public final class GpuPredicates {
     // sampled checks could count offending events but not hand CheckLogger their Java states
     m.set(ValueLayout.JAVA_INT, Dsl.OFF_DO_CHECKS, Dsl.CHECKS_NONE);
     m.set(ValueLayout.JAVA_INT, Dsl.OFF_CHECK_SAMPLE, 0);
+    // the reported terminal only; a caller that wants every terminal of the final level
+    // (GpuBFS.terminals) sets the cap here before Engine.setSettings
+    m.set(ValueLayout.JAVA_INT, Dsl.OFF_MAX_TERMINALS, 0);
     return m;
   }
 

@@ -203,9 +203,8 @@ struct BfsEngine : EngineBase {
   static constexpr int kSegTables = 8;
   // One host round trip (counted in dsl_stats.host_syncs). The host polls the stream instead of
   // blocking in hipStreamSynchronize: a search is ~1 ms of device work with one or two waits, and a
-  // blocked thread's wake-up latency (tens of microseconds, varying by host) is paid per search.
-  // DSL_BLOCKING_SYNC=1 restores the blocking wait.
-  bool spin_sync = !getenv("DSL_BLOCKING_SYNC");
+  // blocked thread's wake-up latency (tens of microseconds, varying by host) is paid per search
+  // (profiles/r03_host_sync_spin_vs_block.txt).
   // With a communicator the wait also polls its asynchronous error and a deadline
   // (DSL_COMM_TIMEOUT_MS, default 300 s, counted once the stream reached its last collective):
   // either aborts the communicator and fails the search.
@@ -235,15 +234,12 @@ struct BfsEngine : EngineBase {
       }
       if (e != hipSuccess) DSL_HIP(e);
       comm->synced();
-    } else if (spin_sync) {
+    } else {
       seg_since_sync = 0;
       hipError_t e;
       while ((e = hipStreamQuery(stream)) == hipErrorNotReady) {
       }
       if (e != hipSuccess) DSL_HIP(e);
-    } else {
-      seg_since_sync = 0;
-      DSL_HIP(hipStreamSynchronize(stream));
     }
     stats.host_syncs++;
     return DSL_OK;
@@ -277,10 +273,8 @@ struct BfsEngine : EngineBase {
     return s;
   }
   // The span a repeated search of this engine wants: 4x the largest frontier the last search
-  // produced, so that one queue covers every level that fits (no host round trip between them);
-  // DSL_QSPAN_FIXED keeps the span at 32x the frontier the queue starts from.
+  // produced, so that one queue covers every level that fits (no host round trip between them).
   uint64_t q_span_want = 0;
-  const bool q_span_adapt = getenv("DSL_QSPAN_FIXED") == nullptr;
   uint64_t q_rows_forced = 0;  // DSL_QUEUE_ROWS (a multiple of 32)
   uint64_t q_span_hint = 0;  // the largest span an earlier queue of this engine used (buffers exist)
   uint64_t queue_flimit(uint64_t span) const {
@@ -292,10 +286,8 @@ struct BfsEngine : EngineBase {
   unsigned char* hq = nullptr;     // pinned copy of the kQueue sets
   std::vector<hipEvent_t> qev;     // brackets the whole queue (no event packets between its levels)
   // HIP events bracket the queue: its device time is expand_ms, which bench.py's roofline divides
-  // by the launches. DSL_NO_QUEUE_EVENTS times the queue on the host instead (launch to drained
-  // stream, ~0.6 % faster per search: profiles/r03_queue_fetch_events.txt)
-  const bool q_events = getenv("DSL_NO_QUEUE_EVENTS") == nullptr;
-  const bool q_memcpy = getenv("DSL_CTR_KERNEL") == nullptr;  // counters by hipMemcpyAsync (k_fetch_counters measured slower)
+  // by the launches (timing the queue on the host instead, launch to drained stream, was ~0.6 %
+  // faster per search: profiles/r03_queue_fetch_events.txt).
   double q_ms_total = 0;           // the last queue's time (expand_ms)
   int q_left = 0, q_pos = 0;
   uint64_t n_reallocs = 0;  // device buffer reallocations (DSL_LEVEL_TRACE)
@@ -513,22 +505,18 @@ struct BfsEngine : EngineBase {
   // the LDS budget of the staged rows.
   // LDS per staged parent: its row, fingerprint, node hashes (kernels.hpp k_level step 2) and offset
   // (+16 per chunk: LdsRow::image rounds the padded row image up to 16 bytes)
-  static constexpr size_t kRowLds = (size_t)LdsRow<P>::kStride * 4 + sizeof(Fp) * (1 + (DSL_NH_LDS ? P::kNodes : 0)) + 4;
+  static constexpr size_t kRowLds = (size_t)LdsRow<P>::kStride * 4 + sizeof(Fp) * (1 + P::kNodes) + 4;
   int pb_max() const {
-#ifndef DSL_PB_PASSES
-#define DSL_PB_PASSES 3
-#endif
-    const int lds_max = (int)((DSL_ROWS_LDS_BYTES) / kRowLds);
-    const int want = (int)((DSL_PB_PASSES * kLevelBlock * 16 + avg_events_x16 - 1) / std::max<uint64_t>(avg_events_x16, 1));
+    const int lds_max = (int)(kRowsLdsBytes / kRowLds);
+    const int want = (int)((3 * kLevelBlock * 16 + avg_events_x16 - 1) / std::max<uint64_t>(avg_events_x16, 1));
     return std::max(1, std::min({want, lds_max, kLevelBlock}));
   }
   // k_level workgroups resident at once on the device with `lds` bytes of dynamic LDS: the
   // occupancy of the protocol's instantiation (registers, LDS) x the CUs -- 1,024 for C5's
   // Multi-Paxos (128 VGPRs: 4 per CU), more for a protocol with small rows and few registers (the
-  // synthetic C3: 48 VGPRs). The grids and the chunk rounds are sized for it. DSL_SLOTS_RT forces it.
+  // synthetic C3: 48 VGPRs). The grids and the chunk rounds are sized for it.
   std::vector<std::pair<uint64_t, int>> slot_cache;
   int level_slots(size_t lds, bool route = false) {
-    if (const char* e = getenv("DSL_SLOTS_RT")) return stats.level_slots = std::max(64, atoi(e));
     const uint64_t key = lds * 2 + (route ? 1 : 0);
     for (auto& kv : slot_cache)
       if (kv.first == key) {
@@ -556,7 +544,7 @@ struct BfsEngine : EngineBase {
   // elapsed_ms: the search's time so far; with a time limit, the queue holds no more levels than
   // the remaining budget covers at the last queue's measured time per level (SearchSettings
   // maxTimeSecs is checked between levels, so a queue never runs far past it).
-  int enqueue_queue(int depth, double growth, double elapsed_ms, int* ran) {
+  int enqueue_queue(int depth, double elapsed_ms, int* ran) {
     Shard& S = sh[0];
     if (!qctr) {
       DSL_HIP(hipMalloc(&qctr, (size_t)(kQueue + 1) * kCtrSet));
@@ -641,25 +629,14 @@ struct BfsEngine : EngineBase {
       a.W = W;
       a.me = S.gid;
       a.owner_filter = 0;
-      if (j == 0 && q_events) DSL_HIP(hipEventRecord(qev[0], stream));
-      // grid: one chunk per workgroup at the predicted frontier size (the kernel loops over more)
-      const double fpred = (double)S.F * std::pow(growth, (double)j);
-      (void)fpred;
-      const int grid = spread;
+      if (j == 0) DSL_HIP(hipEventRecord(qev[0], stream));
+      const int grid = spread;  // the resident workgroups (the kernel loops over the chunks)
       hipLaunchKernelGGL((k_level<P, false>), dim3(grid), dim3(kLevelBlock), lds, stream, a, prm, dset);
       DSL_HIP(hipGetLastError());
     }
-    if (q_events) DSL_HIP(hipEventRecord(qev[1], stream));
+    DSL_HIP(hipEventRecord(qev[1], stream));
     stats.expand_launches += nq;  // every dispatch, also those after the stop (they return at once)
-    if (q_memcpy) {
-      DSL_HIP(hipMemcpyAsync(hq, qctr, (size_t)nq * kCtrSet, hipMemcpyDeviceToHost, stream));
-    } else {
-      static_assert(kCtrSet % 16 == 0, "counter sets are copied in 16-byte units");
-      const int n16 = nq * (kCtrSet / 16);
-      hipLaunchKernelGGL(k_fetch_counters, dim3((n16 + kBlock - 1) / kBlock), dim3(kBlock), 0, stream,
-                         reinterpret_cast<const uint4*>(qctr), reinterpret_cast<uint4*>(hq), n16);
-      DSL_HIP(hipGetLastError());
-    }
+    DSL_HIP(hipMemcpyAsync(hq, qctr, (size_t)nq * kCtrSet, hipMemcpyDeviceToHost, stream));
     DSL_TRY(hsync());
     q_ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count();
     // the levels that ran: up to the first whose counters stop the queue (the device's rule)
@@ -680,7 +657,7 @@ struct BfsEngine : EngineBase {
       }
     }
     float qms = 0;
-    if (q_events && hipEventElapsedTime(&qms, qev[0], qev[1]) == hipSuccess) q_ms_total = qms;
+    if (hipEventElapsedTime(&qms, qev[0], qev[1]) == hipSuccess) q_ms_total = qms;
     q_ms_per_level = q_ms_total / *ran;
     return DSL_OK;
   }
@@ -1314,7 +1291,7 @@ struct BfsEngine : EngineBase {
   // be (W * 32, up to 64) = 16,384 workgroups at W = 8, mostly without a record: dispatching them
   // was most of the launch (C5's level 12: 27 us of k_probe_slab per shard).
   static int slab_gy(int groups, uint64_t per) {
-    static const int total = getenv("DSL_SLAB_BLOCKS") ? std::max(1, atoi(getenv("DSL_SLAB_BLOCKS"))) : 2048;
+    constexpr int total = 2048;
     return (int)std::max<uint64_t>(1, std::min<uint64_t>((per + kBlock - 1) / kBlock,
                                                          (uint64_t)std::max(1, total / std::max(1, groups))));
   }
@@ -1366,8 +1343,7 @@ struct BfsEngine : EngineBase {
     ma.term_cap = term_cap;
     // the grid: the workgroups resident at once (a wave takes 8..PMAX states; more workgroups only
     // launched and left, ~7,000 of 8,192 on C5's sharded levels)
-    static const int mat_blocks = getenv("DSL_MAT_BLOCKS") ? std::max(1, atoi(getenv("DSL_MAT_BLOCKS"))) : 1024;
-    const int blocks = (int)std::min<uint64_t>((std::min(items, room) + kBlock - 1) / kBlock, (uint64_t)mat_blocks);
+    const int blocks = (int)std::min<uint64_t>((std::min(items, room) + kBlock - 1) / kBlock, 1024);
     static const int mat_per = getenv("DSL_MAT_PER") ? std::max(1, std::min(mat_per_max<P>(), atoi(getenv("DSL_MAT_PER")))) : 0;
     ma.per_fixed = mat_per;
     const size_t lds = (size_t)(kBlock / 64) * (mat_per ? mat_per : mat_per_max<P>()) * NW * 4;
@@ -1870,15 +1846,10 @@ struct BfsEngine : EngineBase {
 
         if (use_queue && q_left == 0 && L == 1 && (W == 1 || rep) && sh[0].F > 0 &&
             sh[0].F <= queue_flimit(queue_span(sh[0].F)) && sh[0].work <= 8 * queue_span(sh[0].F)) {
-          // frontier growth per level, for the queued launches' grid sizes
-          const size_t nd = per_depth.size();
-          const double growth =
-              nd >= 2 && per_depth[nd - 2] ? std::max(1.0, (double)per_depth[nd - 1] / per_depth[nd - 2]) : 3.0;
           int ran = 0;
           const auto tq0 = std::chrono::steady_clock::now();
           DSL_TRY(ensure_table(inserted + est_new_states(sh[0].work, prev_new, prev_work)));
-          DSL_TRY(enqueue_queue(depth, growth,
-                                std::chrono::duration<double, std::milli>(tq0 - t_start).count(), &ran));
+          DSL_TRY(enqueue_queue(depth, std::chrono::duration<double, std::milli>(tq0 - t_start).count(), &ran));
           if (trace_levels)
             fprintf(stderr, "[queue] enqueue+run %.4f ms (loop entry %.4f ms after start)\n",
                     std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count(),
@@ -1905,9 +1876,7 @@ struct BfsEngine : EngineBase {
         // a sharded level: the slab (records per source -> owner pair the fast path moves without
         // the host reading any count), from the global work and the last measured routed fraction;
         // identical on every rank (its inputs are). The maxDepth level expands nothing further.
-        // (DSL_LAST_ROUND_B=1, measurement: the maxDepth level like any other, answers back and the
-        // new ones judged at the source by k_materialize, which appends none of them: all PRUNED)
-        const bool last_level = hset.max_depth >= 0 && depth + 1 >= hset.max_depth && !getenv("DSL_LAST_ROUND_B");
+        const bool last_level = hset.max_depth >= 0 && depth + 1 >= hset.max_depth;
         uint64_t slab = 0;  // records per sub-slab (LevelArgs::route_cs)
         if (route && slab_mode) {
           // the most work one rank has: from the last sharded level's records; after replicated
@@ -1919,8 +1888,7 @@ struct BfsEngine : EngineBase {
           // 1.15x the expected records per sub-slab + one wave's 64: every sub-slab takes records of
           // all four wave indexes of many workgroups (k_level), so the fill is even (1.3x before
           // round 6, when a sub-slab took one wave index's records)
-          static const double factor = getenv("DSL_SLAB_FACTOR") ? atof(getenv("DSL_SLAB_FACTOR")) : 1.15;
-          slab = (uint64_t)(factor * frac * per_rank / ((double)W * kRouteSegs)) + 64;
+          slab = (uint64_t)(1.15 * frac * per_rank / ((double)W * kRouteSegs)) + 64;
           if (const char* m = getenv("DSL_SLAB_MAX")) slab = std::min<uint64_t>(slab, std::max(1, atoi(m)));  // tests
         }
         const int lslots = level_slots((size_t)pb_max() * kRowLds + 16, route);
@@ -2165,7 +2133,6 @@ struct BfsEngine : EngineBase {
           stats.work_items += S.lc.work_items;
           stats.new_states += S.lc.new_states;
           stats.probes += S.lc.probes;
-          stats.deduped += S.lc.deduped;
           stats.appended += fn;
           if (S.lc.term_best && recs.empty()) {  // the level's exact best terminal (fold_terminals)
             const uint64_t key = ~(uint64_t)S.lc.term_best;
@@ -2350,21 +2317,19 @@ struct BfsEngine : EngineBase {
     // the search is over and no kernel of it is left to read the tables: zero them now, on the
     // stream, while the host assembles the result and the caller prepares the next search (whose
     // k_setup then only writes the seed); an error return above leaves table_clean false
-    if (!getenv("DSL_SETUP_CLEAR")) {
-      for (auto& S : sh) {
-        DSL_HIP(hipMemsetAsync(S.table, 0, table_buckets * 64, stream));
-        S.table_clean = true;
-      }
-      if (qctr) {
-        DSL_HIP(hipMemsetAsync(qctr, 0, (size_t)(kQueue + 1) * kCtrSet, stream));
-        qctr_clean = true;
-      }
+    for (auto& S : sh) {
+      DSL_HIP(hipMemsetAsync(S.table, 0, table_buckets * 64, stream));
+      S.table_clean = true;
+    }
+    if (qctr) {
+      DSL_HIP(hipMemsetAsync(qctr, 0, (size_t)(kQueue + 1) * kCtrSet, stream));
+      qctr_clean = true;
     }
     if (trace_levels)
       fprintf(stderr, "[clear] %.4f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
     if (x_levels) cost_x_us = x_sum_us / (double)x_levels;
-    if (q_span_adapt && L == 1) {
+    if (L == 1) {
       uint64_t want = kQueueRowsMin;
       while (want < 4 * max_front && want < queue_span_max()) want <<= 1;
       q_span_want = std::max(q_span_want, want);

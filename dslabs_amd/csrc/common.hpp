@@ -38,7 +38,6 @@ constexpr int32_t kOpAnd = -1, kOpOr = -2, kOpNot = -3;
 constexpr uint32_t kReadsAll = 0xffffffffu;
 constexpr int kMaxProgOps = 64;   // ops of all the programs of one search
 constexpr int kMaxProgStack = 16;  // values on a program's stack (2 bits each in one word)
-constexpr int kFlatUnroll = 4;     // leaves judge_view unrolls on a flat program list
 
 // A top-level predicate (an invariant, goal or prune): ops [start, start + len) of the pool.
 struct DevProg {

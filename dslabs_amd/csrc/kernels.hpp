@@ -31,10 +31,7 @@ constexpr int kBlock = 256;
 constexpr int kLevelBlock = 256;
 constexpr uint32_t kTermCap = 1024;  // default TerminalRec entries per shard (DSL_TERM_CAP)
 constexpr int kMaxShards = 16;
-#ifndef DSL_KWIN
-#define DSL_KWIN 1024
-#endif
-constexpr int kWin = DSL_KWIN;  // work items per class-sorted window of k_level
+constexpr int kWin = 1024;  // work items per class-sorted window of k_level
 // a located event in 16 bits: record indices < kNetCap, timers -1 - (node * 256 + j) >= -4096
 constexpr int kEvNone = -32768;
 // The next frontier is written into up to kSegs segments, one reservation counter each (a
@@ -45,36 +42,22 @@ constexpr int kEvNone = -32768;
 constexpr int kSegs = 32;
 // LDS budget for a k_level chunk's staged parent rows: with the kernel's ~11 KB of static LDS, 4
 // resident workgroups per CU (the 4 waves/SIMD the register budget allows) fit in 160 KB.
-#ifndef DSL_ROWS_LDS_KB
-#define DSL_ROWS_LDS_KB 24
-#endif
-#ifndef DSL_ROWS_LDS_BYTES  // the same budget in bytes (measurement builds set it between whole KB)
-#define DSL_ROWS_LDS_BYTES (DSL_ROWS_LDS_KB * 1024)
-#endif
-// 1: the parents' node hashes are computed once per chunk and kept in LDS (80 B per Multi-Paxos
-// parent); 0: every probing lane hashes its changed node's old words itself (more parents per chunk)
-#ifndef DSL_NH_LDS
-#define DSL_NH_LDS 1
-#endif
+// (20 / 24 / 28 KB measured: profiles/r05_rows_lds_ab.txt, profiles/r06_chunk_budget_ab.txt.)
+constexpr int kRowsLdsBytes = 24 * 1024;
 // Row stride of the staged parents in LDS (dwords). A packed row is a multiple of 16 B, and
 // Multi-Paxos's is 160 dwords = 0 mod 32: at stride kWords every lane-per-parent access of word c
 // (node hashes, event counts, classification, the handlers' parent reads) hits bank c mod 32, a
 // 32-way conflict per ds_read_b32 group (2.9 extra LDS cycles per LDS instruction on
-// C5). A row stride padded by DSL_LDS_PAD dwords spreads consecutive parents over the banks:
+// C5). A row stride padded by kPad dwords spreads consecutive parents over the banks:
 //   pad 4 (16-B aligned rows): staged by LDS-DMA, one global_load_lds_dwordx4 per row (lanes over
 //     the row's 16-byte units), 8 distinct banks per 32 parents;
-//   pad 1 / 2: 32 / 16 distinct banks, staged through registers (LDS-DMA writes lane x 16 B);
 //   pad 0: the rows back to back, one DMA instruction per 1 KiB.
-// Default: pad 4 for a protocol whose row is 0 mod 32 dwords and has at least 64 words (one DMA
+// Pad 4 for a protocol whose row is 0 mod 32 dwords and has at least 64 words (one DMA
 // instruction per row is then at least 16 active lanes), else 0.
 template <class P>
 struct LdsRow {
   static constexpr int kWords = Layout<P>::kWords;
-#ifdef DSL_LDS_PAD
-  static constexpr int kPad = DSL_LDS_PAD;
-#else
   static constexpr int kPad = (kWords % 32 == 0 && kWords >= 64) ? 4 : 0;
-#endif
   static constexpr int kStride = kWords + kPad;
   // dwords of a chunk's row image (rounded to 16 B, so the fingerprints after it stay aligned)
   static constexpr int image(int pb) { return (pb * kStride + 3) / 4 * 4; }
@@ -110,7 +93,6 @@ struct LevelCounters {
   unsigned long long time_up;       // the search's deadline passed during this level (it is partial)
   unsigned long long route_spilled; // routed successors past their destination region (rspill list)
   unsigned long long unspilled;     // rows k_unspill appended (multi-shard fast path: device count)
-  unsigned long long deduped;       // successors found in the chunk's LDS set (ChunkDedup): not probed / routed
   unsigned long long phase[12];     // DSL_PHASES builds only: shader cycles per k_level phase
   unsigned long long phcls[32];     // DSL_PHASES: handler cycles per class [0, 16), wave-passes [16, 32)
 };
@@ -233,44 +215,6 @@ __device__ __forceinline__ unsigned long long wave_reserve(unsigned long long* c
   base = rl64(base, leader);
   const unsigned long long lt = (lane == 0) ? 0ull : (mask & ((1ull << lane) - 1ull));
   return base + (unsigned long long)__popcll(lt);
-}
-
-// Workgroup-wide slot reservation on per-destination counters (W <= kMaxShards; W = 1 for a
-// plain append): a lane with `pred` gets a unique index in ctrs[dest]. One returning atomic per
-// destination per call per workgroup, not per wave -- a single device-scope counter word
-// saturates near 90 returning atomics/us on MI355X, so per-wave reservations from every CU
-// serialize the whole level on that word. Has barriers: every thread of the block calls it.
-template <int BS = kBlock>
-struct BlockResv {
-  int cnt[BS / 64][kMaxShards];
-  unsigned long long off[BS / 64][kMaxShards];
-};
-
-template <int BS = kBlock>
-__device__ __forceinline__ unsigned long long block_reserve(BlockResv<BS>& s, unsigned long long* ctrs, bool pred,
-                                                            int dest, int W, int stride = 1) {
-  const int wid = threadIdx.x >> 6, lane = __lane_id();
-  const unsigned long long lt = (1ull << lane) - 1ull;
-  unsigned long long mine = 0;
-  for (int d = 0; d < W; d++) {
-    const bool me = pred && dest == d;
-    const unsigned long long m = __ballot(me);
-    if (lane == 0) s.cnt[wid][d] = __popcll(m);
-    if (me) mine = m;
-  }
-  __syncthreads();
-  if ((int)threadIdx.x < W) {
-    const int d = threadIdx.x;
-    unsigned long long tot = 0;
-    for (int w = 0; w < BS / 64; w++) tot += (unsigned long long)s.cnt[w][d];
-    unsigned long long base = tot ? atomicAdd(&ctrs[(size_t)d * stride], tot) : 0ull;
-    for (int w = 0; w < BS / 64; w++) {
-      s.off[w][d] = base;
-      base += (unsigned long long)s.cnt[w][d];
-    }
-  }
-  __syncthreads();
-  return pred ? s.off[wid][dest] + (unsigned long long)__popcll(mine & lt) : 0ull;
 }
 
 // Wave-level slot reservation on per-destination counters (ctrs[d * stride], d < W <= kMaxShards):
@@ -519,44 +463,6 @@ __device__ __forceinline__ bool lane_emit(bool active, const uint32_t* pw, const
   return __ballot(coll) != 0ull;
 }
 
-// In-chunk duplicate filter (P::kChunkDedup): a chunk's parents are consecutive frontier rows,
-// so siblings sit together, and two interleavings of two independent events of one grandparent
-// (a diamond) reach the same state inside one chunk -- 18 % of the C3 synthetic protocol's probes
-// (tools/cpu_bfs.cpp DSL_CPU_CHUNK_CENSUS, profiles/r06_chunk_census.txt). Every probing lane
-// first inserts its fingerprint's high word into an LDS set of the chunk (a 64-bit LDS CAS,
-// linear probing, at most 8 slots): a lane that finds it there is a successor of this chunk
-// already probed (or routed) by another lane -- the same state (63 fingerprint bits), so not new
-// (Search.java:485: discovered.add returns false) and neither probed nor routed again. A crowded
-// set only lets a duplicate through to the global probe, which answers exactly. A false merge needs
-// two distinct states of one chunk with equal high words: about (items per chunk)^2 / 2^64 per
-// chunk, 3e-8 for the whole C3 d10 search, within the visited table's own bound.
-// P::kChunkDedup enables it on unrouted levels, P::kRouteDedup on sharded (routed) levels, where a
-// duplicate also costs 16 bytes over the links and an owner probe.
-template <class P, class = void>
-struct ChunkDedup : std::false_type {};
-template <class P>
-struct ChunkDedup<P, std::void_t<decltype(P::kChunkDedup)>> : std::integral_constant<bool, P::kChunkDedup> {};
-template <class P, class = void>
-struct RouteDedup : std::false_type {};
-template <class P>
-struct RouteDedup<P, std::void_t<decltype(P::kRouteDedup)>> : std::integral_constant<bool, P::kRouteDedup> {};
-#ifndef DSL_DEDUP_SLOTS
-#define DSL_DEDUP_SLOTS 1024
-#endif
-constexpr int kDedupSlots = DSL_DEDUP_SLOTS;  // a power of two
-__device__ __forceinline__ bool chunk_seen(unsigned long long* set, const Fp& f) {
-  const unsigned long long key = f.hi | 1ull;  // never 0 (an empty slot)
-  uint32_t h = (uint32_t)f.lo & (uint32_t)(kDedupSlots - 1);
-#pragma unroll 1
-  for (int i = 0; i < 8; i++) {
-    const unsigned long long old = atomicCAS(set + h, 0ull, key);
-    if (old == 0ull) return false;
-    if (old == key) return true;
-    h = (h + 1u) & (uint32_t)(kDedupSlots - 1);
-  }
-  return false;
-}
-
 template <class P>
 struct LevelArgs {
   const uint32_t* cur;       // frontier rows of kWords (row ranges in `segs`)
@@ -686,39 +592,6 @@ __device__ __forceinline__ void stage_rows_dma(const uint4* src, uint32_t* dst, 
   }
 }
 
-// Copies a chunk's rows (pb rows of NW dwords, contiguous in global memory) into an LDS image of
-// row stride SP > NW through registers: every thread issues all its 16-byte loads before its first
-// LDS store (the chunk is at most DSL_ROWS_LDS_KB, i.e. a fixed number of units per thread).
-template <int NW, int SP>
-__device__ __forceinline__ void stage_rows_padded(const uint4* src, uint32_t* dst, int pb) {
-  constexpr int U = NW / 4;  // 16-byte units per row
-  constexpr int kIt = (DSL_ROWS_LDS_BYTES / 16 + kLevelBlock - 1) / kLevelBlock;
-  const int n16 = pb * U;
-  uint4 v[kIt];
-#pragma unroll
-  for (int it = 0; it < kIt; it++) {
-    const int u = (int)threadIdx.x + it * kLevelBlock;
-    if (u < n16) v[it] = src[u];
-  }
-#pragma unroll
-  for (int it = 0; it < kIt; it++) {
-    const int u = (int)threadIdx.x + it * kLevelBlock;
-    if (u < n16) {
-      const int j = u / U, c = u - j * U;
-      uint32_t* o = dst + j * SP + 4 * c;
-      if constexpr (SP % 2 == 0) {
-        reinterpret_cast<uint2*>(o)[0] = make_uint2(v[it].x, v[it].y);
-        reinterpret_cast<uint2*>(o)[1] = make_uint2(v[it].z, v[it].w);
-      } else {
-        o[0] = v[it].x;
-        o[1] = v[it].y;
-        o[2] = v[it].z;
-        o[3] = v[it].w;
-      }
-    }
-  }
-}
-
 // Terminal candidates of a level are reduced EXACTLY by priority (EXCEPTION > INVARIANT > GOAL,
 // Search.java:370-385), then by the successor's fingerprint (a deterministic tie-break): a wave
 // takes the minimum key of its candidates and folds it into LevelCounters::term_best with one
@@ -768,69 +641,43 @@ template <class P, class = void>
 struct LevelWaves : std::integral_constant<int, 4> {};
 template <class P>
 struct LevelWaves<P, std::void_t<decltype(P::kLevelWaves)>> : std::integral_constant<int, P::kLevelWaves> {};
-#ifndef DSL_KLEVEL_ATTR
-#define DSL_KLEVEL_ATTR __attribute__((amdgpu_waves_per_eu(LevelWaves<P>::value)))
-#endif
 template <class P, bool ROUTE>
-__global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
+__global__ void __launch_bounds__(kLevelBlock) __attribute__((amdgpu_waves_per_eu(LevelWaves<P>::value)))
+k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
   constexpr int NW = Layout<P>::kWords;
   constexpr int SP = LdsRow<P>::kStride;  // row stride of the staged parents in LDS
   constexpr int NWAVE = kLevelBlock / 64;
   // handler classes: messages, timers, then the events whose handler surely changes nothing
   // (NoopFilter: counted as successors and never run; they sort last and the passes stop before them)
   constexpr int NC = Classes<P>::kCount;
-  constexpr bool kDD = ROUTE ? RouteDedup<P>::value : ChunkDedup<P>::value;  // the in-chunk duplicate filter
   static_assert(P::kNodes * 256 < 32768 && P::kNetCap < 32768, "a located event fits s_ev's 16 bits");
   extern __shared__ __align__(16) uint32_t lds[];
   uint32_t* rows = lds;                                           // a.PB (max) rows, stride SP
   Fp* fps = reinterpret_cast<Fp*>(rows + LdsRow<P>::image(a.PB));  // a.PB
-  constexpr int kNhPer = DSL_NH_LDS ? P::kNodes : 0;
-  Fp* nh = fps + a.PB;                                     // a.PB * kNodes: the parents' node hashes
-  int* off = reinterpret_cast<int*>(nh + a.PB * kNhPer);   // a.PB + 1
+  Fp* nh = fps + a.PB;                                       // a.PB * kNodes: the parents' node hashes
+  int* off = reinterpret_cast<int*>(nh + a.PB * P::kNodes);  // a.PB + 1
   __shared__ SegTable s_segs;
-  __shared__ BlockResv<kLevelBlock> s_resv;
   __shared__ uint32_t s_nodew[kLevelBlock * P::kNodeWords];
   __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kLevelBlock * P::kMaxSends : 1];
 #ifdef DSL_PHASES
   __shared__ unsigned long long s_red[NWAVE];  // PH_FLUSH (instrumented builds)
 #endif
-  __shared__ unsigned long long s_red5[NWAVE * 6];
+  __shared__ unsigned long long s_red5[NWAVE * 6];  // the five exit sums per wave, rows of 6 words
   __shared__ int s_wsum[NWAVE];
-#ifndef DSL_SORT_BALLOT
   // the window's class counts (LDS atomics in step 3a, each item's rank within its class in s_rnk)
   __shared__ int s_ccnt[16], s_cbase0[16];
   __shared__ uint16_t s_rnk[kWin];
-  __shared__ int s_cbase[1][NC];
-#else
-  __shared__ int s_cbase[kWin / 64][NC];
-#endif
   __shared__ uint8_t s_par[kWin], s_cls[kWin];
   __shared__ uint16_t s_perm[kWin];
   __shared__ int16_t s_ev[kWin];  // each item's located event (locate_event code; kEvNone: none)
   __shared__ int s_stop, s_weff, s_gnext, s_tup;
   __shared__ uint64_t s_t0;
-  __shared__ unsigned long long s_dd[kDD ? kDedupSlots : 1];
   const int tid = threadIdx.x, lane = __lane_id(), wid = tid >> 6;
   const bool find = a.find != 0;
   // per-thread statistics, flushed once per workgroup (no per-wave atomics on shared words)
-  uint32_t c_succ = 0, c_new = 0, c_next_work = 0, c_work = 0, c_probe = 0, c_dup = 0;
+  uint32_t c_succ = 0, c_new = 0, c_next_work = 0, c_work = 0, c_probe = 0;
   PH_DECL
   PH_CLS_DECL
-#ifdef DSL_KWARM
-  {  // (measurement variant) every 64-byte line of the kernel arguments, independent scalar loads
-    uint32_t acc = 0;
-    const uint32_t* ks = reinterpret_cast<const uint32_t*>(&set);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(DevSettings) / 4); i += 16) acc += ks[i];
-    const uint32_t* kp = reinterpret_cast<const uint32_t*>(&prm);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(prm) / 4); i += 16) acc += kp[i];
-    const uint32_t* ka = reinterpret_cast<const uint32_t*>(&a);
-#pragma unroll
-    for (int i = 0; i < (int)(sizeof(a) / 4); i += 16) acc += ka[i];
-    asm volatile("" ::"s"(acc));
-  }
-#endif
   if (a.qprev) {
     // queued level: this frontier is the previous level's segments; every workgroup derives the
     // table (and whether the queue stopped) from those counters, as the host does afterwards
@@ -860,9 +707,7 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
     if (tid == 0) s_stop = 0;
   }
   if (a.budget_rt && tid == 0) s_t0 = *a.t0_rt;
-#ifndef DSL_SORT_BALLOT
   if (tid < 16) s_ccnt[tid] = 0;
-#endif
   __syncthreads();
   if (s_stop) return;  // an earlier queued level stopped the queue
   PH_MARK(8);  // prologue: the frontier's segment table (+ the queue rule)
@@ -877,7 +722,6 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
   int g = 0;
   int npass = 0;  // this workgroup's passes so far (ROUTE: its sub-slab rotates with them)
   for (uint64_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-#ifndef DSL_NO_LANE_REMAT
     // the lane indices as values opaque to the compiler, once per chunk: the per-lane addresses
     // derived from them are recomputed where used instead of held live (and spilled) across
     // chunks (C5 d12 scratch 36 -> 20 B/lane, C3 d10 60 -> 12 B/lane and +1.1 %:
@@ -885,7 +729,6 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
     int tid_c = tid, lane_c = lane;
     asm volatile("" : "+v"(tid_c), "+v"(lane_c));
     const int tid = tid_c, lane = lane_c, wid = tid_c >> 6;
-#endif
     if (a.budget_rt) {  // the deadline, before every chunk (one workgroup-uniform decision)
       if (tid == 0) s_tup = __builtin_amdgcn_s_memrealtime() - s_t0 > a.budget_rt ? 1 : 0;
       __syncthreads();
@@ -902,13 +745,9 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
     //    before the one wait
     if constexpr (SP == NW)
       stage_lds(reinterpret_cast<const uint4*>(a.cur + p0 * NW), reinterpret_cast<uint4*>(rows), pb * NW / 4);
-    else if constexpr (SP % 4 == 0)
-      stage_rows_dma<NW, SP>(reinterpret_cast<const uint4*>(a.cur + p0 * NW), rows, pb);
     else
-      stage_rows_padded<NW, SP>(reinterpret_cast<const uint4*>(a.cur + p0 * NW), rows, pb);
+      stage_rows_dma<NW, SP>(reinterpret_cast<const uint4*>(a.cur + p0 * NW), rows, pb);
     stage_lds(reinterpret_cast<const uint4*>(a.cur_fp + p0), reinterpret_cast<uint4*>(fps), pb);
-    if constexpr (kDD)  // the chunk's duplicate filter starts empty (the staging barrier publishes it)
-      for (int i = tid; i < kDedupSlots; i += kLevelBlock) s_dd[i] = 0ull;
     __builtin_amdgcn_s_waitcnt(0);
     __syncthreads();
     PH_MARK(9);  // staging (LDS-DMA + wait + barrier)
@@ -916,18 +755,18 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
     //    term of the incremental fingerprint: fp ^ H(i, old) ^ H(i, new) ^ ...), one lane per
     //    (parent, node); then the enabled events per parent (SearchState.events) and a workgroup
     //    exclusive scan (wave scans); the scan's barrier also publishes the hashes
-#ifndef DSL_CNT_SERIAL  // a chunk of <= 64 parents: waves 1-3 hash while wave 0 counts (+0.7 % on C5 d12)
-    if (!DSL_NH_LDS) {
-    } else if (pb <= 64) {
+    //    (a chunk of <= 64 parents: waves 1-3 hash while wave 0 counts, +0.7 % on C5 d12,
+    //    profiles/r06_cls_split_cnt_ab.txt)
+    if (pb <= 64) {
       for (int x = tid - 64; x >= 0 && x < pb * P::kNodes; x += kLevelBlock - 64) {
         const int jj = x / P::kNodes, ii = x - jj * P::kNodes;
         nh[x] = node_hash<P>(ii, rows + jj * SP + ii * P::kNodeWords);
       }
-    } else
-#endif
-    for (int x = tid; x < pb * kNhPer; x += kLevelBlock) {
-      const int jj = x / P::kNodes, ii = x - jj * P::kNodes;
-      nh[x] = node_hash<P>(ii, rows + jj * SP + ii * P::kNodeWords);
+    } else {
+      for (int x = tid; x < pb * P::kNodes; x += kLevelBlock) {
+        const int jj = x / P::kNodes, ii = x - jj * P::kNodes;
+        nh[x] = node_hash<P>(ii, rows + jj * SP + ii * P::kNodeWords);
+      }
     }
     int total;
     if (pb <= 64) {  // one wave's worth of parents: wave 0 scans them alone, one barrier
@@ -984,7 +823,8 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
           const int lo = max(e0, w0), hi = min(off[j + 1], w0 + wn);
           const uint32_t* w = rows + j * SP;
           int q = lo + sub;
-#ifndef DSL_CLS_ONE_LOOP  // message events first, by a branch-free body, then the timers (+1.3 % on C5 d12)
+          // message events first, by a branch-free body, then the timers (+1.3 % on C5 d12,
+          // profiles/r06_cls_split_cnt_ab.txt)
           if (set.all_deliver) {  // event k < size is record k (SearchState.events: messages first)
             const int mhi = min(hi, e0 + (int)Net<P>::size(w));
             const int nn = P::num_nodes(prm);
@@ -995,23 +835,16 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
               const int cls = skip ? Classes<P>::kSkip : P::msg_class(r);
               s_par[q - w0] = (uint8_t)j;
               s_cls[q - w0] = (uint8_t)cls;
-#ifndef DSL_SORT_BALLOT
               s_rnk[q - w0] = (uint16_t)atomicAdd(&s_ccnt[cls], 1);
-#endif
               s_ev[q - w0] = (int16_t)(q - e0);
             }
           }
-#endif
           for (; q < hi; q += tpp) {
             int ev;
             s_par[q - w0] = (uint8_t)j;
-#ifndef DSL_SORT_BALLOT
             const int cls = event_class_skip<P>(w, prm, set, q - e0, &ev);
             s_cls[q - w0] = (uint8_t)cls;
             s_rnk[q - w0] = (uint16_t)atomicAdd(&s_ccnt[cls], 1);
-#else
-            s_cls[q - w0] = (uint8_t)event_class_skip<P>(w, prm, set, q - e0, &ev);
-#endif
             s_ev[q - w0] = (int16_t)(ev == INT32_MIN ? kEvNone : ev);
           }
         }
@@ -1023,8 +856,8 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
       // 3b. the window sorted by class: one 64-item group is ranked by wave 0 alone with ballots;
       //     a larger window by its LDS-atomic class counts (step 3a: each item's rank within its
       //     class, s_rnk), the class bases by one wave, then one scatter pass -- two barriers and
-      //     no per-group ballots (C5 d12 1.54 -> 1.60e9 states/s, profiles/r06_sort_atomic_ab.txt;
-      //     the per-group ballot sort of rounds 2-5 stays as -DDSL_SORT_BALLOT)
+      //     no per-group ballots (C5 d12 1.54 -> 1.60e9 states/s against the per-group ballot sort
+      //     of rounds 2-5, profiles/r06_sort_atomic_ab.txt)
       const int ng = (wn + 63) >> 6;
       if (ng == 1) {
         // one group (every small level): wave 0 sorts it alone, in registers, with one barrier
@@ -1046,78 +879,29 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
           }
           const int b = __shfl(run, c < 0 ? 0 : c);
           if (lane < wn) s_perm[b + rank] = (uint16_t)lane;
-#ifndef DSL_SORT_BALLOT
           if (lane < 16) s_ccnt[lane] = 0;
-#endif
         }
         __syncthreads();
       } else {
-#ifndef DSL_SORT_BALLOT
-      // counting sort from the LDS-atomic class counts of step 3a: bases by one wave, then every
-      // item to its class base + its rank (the order within a class is the atomics' order)
-      if (tid < 64) {
-        const int cnt = lane < NC ? s_ccnt[lane] : 0;
-        const int inc = (int)row_incl_sum((uint32_t)cnt);
-        const int run = inc - cnt;
-        if (lane == NC - 1) {  // the skipped events: counted, never run
-          s_weff = run;
-          s_gnext = 0;
-          c_succ += (uint32_t)cnt;
-        }
-        if (lane < 16) {
-          s_cbase0[lane] = run;
-          s_ccnt[lane] = 0;
-        }
-      }
-      __syncthreads();
-      for (int t = tid; t < wn; t += kLevelBlock) s_perm[s_cbase0[s_cls[t]] + s_rnk[t]] = (uint16_t)t;
-      __syncthreads();
-#else
-      for (int gr = wid; gr < ng; gr += NWAVE) {
-        const int t = gr * 64 + lane;
-        const int c = t < wn ? (int)s_cls[t] : -1;
-        int mine = 0;
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-          const int n = __popcll(__ballot(c == q));
-          if (lane == q) mine = n;
-        }
-        if (lane < NC) s_cbase[gr][lane] = mine;
-      }
-      __syncthreads();
-      if (tid < 64) {
-        int tot = 0;
-        if (lane < NC)
-          for (int gr = 0; gr < ng; gr++) tot += s_cbase[gr][lane];
-        const int inc = (int)row_incl_sum((uint32_t)tot);
-        int run = inc - tot;
-        if (lane == NC - 1) {  // the skipped events: counted, never run
-          s_weff = run;
-          s_gnext = 0;
-          c_succ += (uint32_t)tot;
-        }
-        if (lane < NC)
-          for (int gr = 0; gr < ng; gr++) {
-            const int v = s_cbase[gr][lane];
-            s_cbase[gr][lane] = run;
-            run += v;
+        // counting sort from the LDS-atomic class counts of step 3a: bases by one wave, then every
+        // item to its class base + its rank (the order within a class is the atomics' order)
+        if (tid < 64) {
+          const int cnt = lane < NC ? s_ccnt[lane] : 0;
+          const int inc = (int)row_incl_sum((uint32_t)cnt);
+          const int run = inc - cnt;
+          if (lane == NC - 1) {  // the skipped events: counted, never run
+            s_weff = run;
+            s_gnext = 0;
+            c_succ += (uint32_t)cnt;
           }
-      }
-      __syncthreads();
-      // 3c. the permutation: class base + rank among the group's lanes of the same class
-      for (int gr = wid; gr < ng; gr += NWAVE) {
-        const int t = gr * 64 + lane;
-        const int c = t < wn ? (int)s_cls[t] : -1;
-        int rank = 0;
-#pragma unroll
-        for (int q = 0; q < NC; q++) {
-          const unsigned long long mq = __ballot(c == q);
-          if (c == q) rank = __popcll(mq & ((1ull << lane) - 1ull));
+          if (lane < 16) {
+            s_cbase0[lane] = run;
+            s_ccnt[lane] = 0;
+          }
         }
-        if (t < wn) s_perm[s_cbase[gr][c] + rank] = (uint16_t)t;
-      }
-      __syncthreads();
-#endif
+        __syncthreads();
+        for (int t = tid; t < wn; t += kLevelBlock) s_perm[s_cbase0[s_cls[t]] + s_rnk[t]] = (uint16_t)t;
+        __syncthreads();
       }
       PH_MARK(7);  // classify + sort
       const int wrun = s_weff;  // the window's events whose handler runs (a prefix of s_perm)
@@ -1129,15 +913,7 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
       // waves finish the window together whatever their handlers cost (a fixed share per wave
       // left the others waiting at the window's barrier). ROUTE levels too: their reservations are
       // per wave (wave_reserve_dest).
-#ifdef DSL_NO_DYN  // measurement variant: fixed shares in every level
-      const bool dyn = false;
-#else
-#ifdef DSL_ROUTE_BLOCK  // measurement variant: workgroup-wide route reservations, fixed shares
-      const bool dyn = !ROUTE && !spread;
-#else
       const bool dyn = !spread;
-#endif
-#endif
       for (int base = 0;;) {
         int t;
         bool live;
@@ -1185,8 +961,7 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
               dn = delta_new_count<P>(d);
               noop = dn == 0 && same_words<P::kNodeWords>(d.nw, w + dnode * P::kNodeWords);
               if (!noop) {
-                if constexpr (DSL_NH_LDS) f = delta_fingerprint_cached<P>(fp_xor(fps[j], nh[j * P::kNodes + dnode]), d);
-                else f = delta_fingerprint<P>(w, fps[j], d);
+                f = delta_fingerprint_cached<P>(fp_xor(fps[j], nh[j * P::kNodes + dnode]), d);
                 // the changed node's words go through LDS: a view pointing at the register
                 // array would take its address and push the whole delta into scratch
 #pragma unroll
@@ -1197,17 +972,9 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
           if (rc == STEP_OK) c_succ++;
           if (rc == STEP_OK && !noop) {
             PH_MARK(2);  // fingerprint
-            // a successor of this chunk seen before (ChunkDedup): the same state, not new; it was
-            // probed or routed once already
-            bool dup = false;
-            if constexpr (kDD) dup = !find && chunk_seen(s_dd, f);
-            c_dup += dup ? 1u : 0u;
             if (ROUTE) dest = owner_of(f, a.W);
             bool judge = false;
-            bool spec = false;  // judged while the home slot's CAS is in flight (DSL_JUDGE_OVERLAP)
-            unsigned long long spec_old = 0ull, spec_key = 0ull;
-            if (dup) {
-            } else if (ROUTE) {
+            if (ROUTE) {
               // a sharded level routes EVERY successor, its own shard's too: the owner probes them
               // all in one interleaved pass (k_probe_slab), so which source wins a state generated
               // by several is a fair race, and the shards' frontiers stay balanced (a local insert
@@ -1220,66 +987,39 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
               judge = a.judge_routed != 0;
             } else {
               c_probe++;
-#ifdef DSL_JUDGE_OVERLAP
-              if (!find && !a.table.load_first) {
-                // the home slot's CAS is issued now and its answer used after the judge, which every
-                // probing lane runs meanwhile (its verdict counts only for a new state)
-                spec_key = table_key0(a.table, f);
-                spec_old = atomicCAS(a.table.slots + table_home(a.table, f), 0ull, spec_key);
-                spec = true;
+              const int ins = find ? INS_NEW : table_insert(a.table, f);
+              PH_MARK(3);  // visited-table probe / insert
+              if (ins == INS_NEW) {
+                c_new++;
                 judge = true;
-              } else
-#endif
-              {
-                const int ins = find ? INS_NEW : table_insert(a.table, f);
-                PH_MARK(3);  // visited-table probe / insert
-                if (ins == INS_NEW) {
-                  c_new++;
-                  judge = true;
-                } else if (ins == INS_FULL) {
-                  atomicAdd(&a.ctr->err_table, 1ull);
-                }
+              } else if (ins == INS_FULL) {
+                atomicAdd(&a.ctr->err_table, 1ull);
               }
             }
             if (judge) {
-              {
-                int pi = -1;
-                NodeView view{w, P::kNodeWords, dnode, my_nw};
-                if constexpr (NetPreds<P>::value) {  // the new records through LDS (no register addresses)
-                  typename P::Rec* ms = s_sends + tid * P::kMaxSends;
-                  int c = 0;
+              int pi = -1;
+              NodeView view{w, P::kNodeWords, dnode, my_nw};
+              if constexpr (NetPreds<P>::value) {  // the new records through LDS (no register addresses)
+                typename P::Rec* ms = s_sends + tid * P::kMaxSends;
+                int c = 0;
 #pragma unroll
-                  for (int q = 0; q < P::kMaxSends; q++)
-                    if ((d.keep >> q) & 1u) ms[c++] = d.out.r[q];
-                  view.sends = ms;
-                  view.nsends = dn;
+                for (int q = 0; q < P::kMaxSends; q++)
+                  if ((d.keep >> q) & 1u) ms[c++] = d.out.r[q];
+                view.sends = ms;
+                view.nsends = dn;
+              }
+              const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
+              if (v == V_VALID) {
+                if (route) {
+                } else if (Net<P>::size(w) + dn <= P::kNetCap) {
+                  is_valid = !find;
+                } else {
+                  atomicAdd(&a.ctr->err_overflow, 1ull);
                 }
-#ifdef DSL_X0_JUDGE  // cost probe (measurement builds): no judge (every new state VALID below maxDepth)
-                const int v = set.max_depth >= 0 && a.depth >= set.max_depth ? V_PRUNED : V_VALID;
-                (void)view;
-#else
-                const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
-#endif
-                bool use = true;
-                if (spec) {  // the probe's answer: the home slot held nothing (new), this key, or another one
-                  const int ins = spec_old == 0ull ? INS_NEW : spec_old == spec_key ? INS_EXISTS : table_insert(a.table, f, 1);
-                  if (ins == INS_NEW) c_new++;
-                  else if (ins == INS_FULL) atomicAdd(&a.ctr->err_table, 1ull);
-                  use = ins == INS_NEW;
-                }
-                if (!use) {
-                } else if (v == V_VALID) {
-                  if (route) {
-                  } else if (Net<P>::size(w) + dn <= P::kNetCap) {
-                    is_valid = !find;
-                  } else {
-                    atomicAdd(&a.ctr->err_overflow, 1ull);
-                  }
-                } else if (v >= V_TERM_EXCEPTION) {
-                  tv = v;
-                  tpi = pi;
-                  tkey = term_key(v, f.hi);
-                }
+              } else if (v >= V_TERM_EXCEPTION) {
+                tv = v;
+                tpi = pi;
+                tkey = term_key(v, f.hi);
               }
             }
           } else if (rc == STEP_EXCEPTION) {
@@ -1318,9 +1058,6 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
           else coll = wave_emit<P, SP>(fits, rows, (uint64_t)j, d, a.next + idx * NW, s_nodew + (tid - lane) * P::kNodeWords);
           if (coll && lane == 0)
             atomicAdd(&a.ctr->err_overflow, 1ull);  // two equal kept sends (see wave_emit)
-#ifdef DSL_X2_EMIT  // cost probe (measurement builds): the same rows written twice
-          wave_emit<P, SP>(fits, rows, (uint64_t)j, d, a.next + idx * NW);
-#endif
           PH_MARK(6);  // history + row emission
           // beyond the segment's rows: spill (parent, event); materialized after the level (rare)
           const bool spill = is_valid && !fits;
@@ -1336,13 +1073,6 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
           // region `dest`, sub-slab `sub` (see RouteCounters); a record past its sub-slab goes to
           // the route-spill list (parent, event), which the host re-routes after the level
           // (BfsEngine::complete_sharded; rare)
-          // the workgroup's sub-slab rotates with its passes, so one workgroup's records (a small
-          // level has few workgroups) spread over every sub-slab
-#ifdef DSL_ROUTE_BLOCK
-          const int sub = (int)((blockIdx.x + (unsigned)npass++) % kRouteSegs);
-          const unsigned long long ridx = block_reserve<kLevelBlock>(s_resv, a.rc->out + rc_idx(0, sub), route, dest,
-                                                                     a.W, kRouteSegs * kRouteStride);
-#else
           // by wave: the wave's sub-slab rotates with its passes and with the workgroup, so every
           // sub-slab takes records of all four waves of many workgroups (blockIdx * 4 + wid gave
           // sub-slab q only wave q % 4's records: in a one-round level each wave routes its own
@@ -1351,7 +1081,6 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
           const int sub = (int)((blockIdx.x + (unsigned)wid * (kRouteSegs / NWAVE) + (unsigned)npass++) % kRouteSegs);
           const unsigned long long ridx = wave_reserve_dest(a.rc->out + rc_idx(0, sub), route, dest, a.W,
                                                             kRouteSegs * kRouteStride);
-#endif
           if (route) {
             const uint64_t item = ((p0 + j) << 20) | (uint64_t)k;
             if (ridx < a.route_cs) {
@@ -1380,14 +1109,13 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
     PH_MARK(10);  // end-of-window / end-of-chunk barrier waits
   }
   {  // the statistics in one workgroup reduction (one barrier pair, one atomic each)
-    constexpr int NS = kDD ? 6 : 5;
+    constexpr int NS = 5;
     uint32_t v[NS];
     v[0] = wave_sum(c_succ);
     v[1] = wave_sum(c_new);
     v[2] = wave_sum(c_next_work);
     v[3] = wave_sum(c_work);
     v[4] = wave_sum(c_probe);
-    if constexpr (NS > 5) v[5] = wave_sum(c_dup);
     __syncthreads();
     if (lane == 0)
 #pragma unroll
@@ -1398,7 +1126,7 @@ __global__ void __launch_bounds__(kLevelBlock) DSL_KLEVEL_ATTR k_level(LevelArgs
       for (int w = 0; w < NWAVE; w++) t += s_red5[w * 6 + tid];
       unsigned long long* dst = tid == 0 ? &a.ctr->successors : tid == 1 ? &a.ctr->new_states
                                 : tid == 2 ? &a.ctr->next_work : tid == 3 ? &a.ctr->work_items
-                                : tid == 4 ? &a.ctr->probes : &a.ctr->deduped;
+                                : &a.ctr->probes;
       if (t) atomicAdd(dst, t);
     }
   }
@@ -1494,15 +1222,6 @@ __global__ void __launch_bounds__(kBlock) k_setup(SetupArgs<P> a) {
       if (threadIdx.x == 0) *a.cur_fp = a.fp;
     }
   }
-}
-
-// The queue's counter sets to the pinned host copy (BfsEngine::enqueue_queue), launched on the
-// stream right behind the queued levels. A hipMemcpyAsync's blit kernel started ~12 us after the
-// last level (rocprofv3 kernel trace); a kernel follows back-to-back like the levels do. The
-// system-scope fence makes the stores visible to the host before the kernel completes.
-__global__ void __launch_bounds__(kBlock) k_fetch_counters(const uint4* __restrict__ src, uint4* dst, int n16) {
-  for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += gridDim.x * blockDim.x) dst[i] = src[i];
-  __threadfence_system();
 }
 
 // Visited-table growth (a level boundary, BfsEngine::ensure_table): every key of `from` into the

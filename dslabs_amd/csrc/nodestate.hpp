@@ -117,19 +117,11 @@ struct Sender {
       overflow = true;
       return;
     }
-#ifdef DSL_SENDER_SHIFT
-    // shift register: the newest record at r[0] (the lanes at this send site move, the others keep
-    // their registers under the exec mask; no compare with n per slot)
-#pragma unroll
-    for (int i = K - 1; i > 0; i--) r[i] = r[i - 1];
-    r[0] = x;
-#else
 #pragma unroll
     for (int i = 0; i < K; i++) {
       if (wave_none(i <= n)) break;  // every sending lane's slot is behind
       r[i] = keep_value(i == n ? x : r[i]);
     }
-#endif
     n++;
   }
 };
@@ -640,14 +632,12 @@ struct EvalHeld {
     return P::eval(pr, v, prm);
   }
 };
-#ifndef DSL_NO_EVAL_HELD  // (measurement builds: -DDSL_NO_EVAL_HELD evaluates every leaf in full)
 template <class P>
 struct EvalHeld<P, std::void_t<decltype(&P::eval_held)>> {
   static DSL_HD int eval(const DevPred& pr, const NodeView& v, const typename P::Params& prm, bool held) {
     return P::eval_held(pr, v, prm, held);
   }
 };
-#endif
 
 // checkState order over a node view (Search.java:162-231).
 // incremental: the view is a successor of an EXPANDED, non-initial parent, which therefore had
@@ -668,20 +658,10 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
     v.ndropped = set.n_dropped;
   }
   const int ng = set.n_inv + set.n_goal, nt = ng + set.n_prune;
-#ifdef DSL_NO_FLAT  // measurement variant: the program interpreter for every predicate list
-  if (false) {
-#else
   if (set.flat) {
-#endif
     // every program is one leaf (resolve_settings): program t IS ops[t], in checkState order
     // (invariants, goals, prunes) -- no program descriptors, no stack machine
-#ifdef DSL_FLAT_UNROLL
-#pragma unroll
-    for (int t = 0; t < kFlatUnroll; t++) {
-      if (t >= nt) break;
-#else
     for (int t = 0; t < nt; t++) {
-#endif
       const DevPred& op = set.ops[t];
       if (incremental && v.changed >= 0 && leaf_unchanged<P>(op, v)) continue;
       int x = EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
@@ -700,27 +680,6 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
         return V_PRUNED;  // true or throwing
       }
     }
-#ifdef DSL_FLAT_UNROLL
-    for (int t = kFlatUnroll; t < nt; t++) {
-      const DevPred& op = set.ops[t];
-      if (incremental && v.changed >= 0 && leaf_unchanged<P>(op, v)) continue;
-      int x = EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
-      if (x != PV_THREW && op.negate) x = !x;
-      if (t < set.n_inv) {
-        if (x != PV_TRUE) {
-          *pred_index = t;
-          return V_TERM_INVARIANT;
-        }
-      } else if (t < ng) {
-        if (x == PV_TRUE) {
-          *pred_index = t - set.n_inv;
-          return V_TERM_GOAL;
-        }
-      } else if (x != PV_FALSE) {
-        return V_PRUNED;
-      }
-    }
-#endif
     if (set.max_depth >= 0 && depth >= set.max_depth) return V_PRUNED;
     return V_VALID;
   }

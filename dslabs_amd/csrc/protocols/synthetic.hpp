@@ -18,33 +18,16 @@
 
 namespace dsl {
 
-// k_level at 6 waves per SIMD (80 VGPRs): as fast as 8 (64 VGPRs) on C3 d10 with half the scratch
-// (60 vs 124 B per lane; profiles/r06_c3_dedup_waves_ab.txt)
-#ifndef DSL_SYNTH_WAVES
-#define DSL_SYNTH_WAVES 6
-#endif
-
 struct Synthetic {
   static constexpr int kMaxNodes = 5;
   static constexpr int kNodes = kMaxNodes, kNodeWords = 2, kNetCap = kMaxNodes, kMaxSends = 1;
-  static constexpr int kLevelWaves = DSL_SYNTH_WAVES;  // k_level waves per SIMD (kernels.hpp LevelWaves)
-// k_level's in-chunk duplicate filter (kernels.hpp ChunkDedup): off. 18 % of C3's probes are
-// in-chunk duplicates (profiles/r06_chunk_census.txt), but the filter measured 7 % slower on C3 d10
-// (profiles/r06_c3_dedup_waves_ab.txt): every probing lane pays its LDS CAS chain, and a
-// duplicate's global probe is cheap (its line was just touched by the first occurrence).
-#ifndef DSL_SYNTH_DEDUP
-#define DSL_SYNTH_DEDUP 0
-#endif
-  static constexpr bool kChunkDedup = DSL_SYNTH_DEDUP;
-  // on sharded levels the filter would keep duplicates off the links (16 B each) and the owners'
-  // probes -- but the device's frontier order leaves few of them in a chunk (siblings are emitted
-  // by different waves and passes, interleaved with other workgroups' rows): with the filter on, C3
-  // d9 at W = 8 routed 549.7 M instead of 551.5 M records, while its k_level took 13 % longer
-  // (profiles/r06_shard_scale.txt). Off.
-#ifndef DSL_SYNTH_ROUTE_DEDUP
-#define DSL_SYNTH_ROUTE_DEDUP 0
-#endif
-  static constexpr bool kRouteDedup = DSL_SYNTH_ROUTE_DEDUP;
+  // k_level waves per SIMD (kernels.hpp LevelWaves): 6 (80 VGPRs) is as fast as 8 (64 VGPRs) on C3
+  // d10 with half the scratch (60 vs 124 B per lane; profiles/r06_c3_dedup_waves_ab.txt)
+  static constexpr int kLevelWaves = 6;
+  // (An in-chunk duplicate filter in LDS measured slower: 18 % of C3's probes are in-chunk
+  // duplicates, profiles/r06_chunk_census.txt, but with the filter C3 d10 ran 7 % slower,
+  // profiles/r06_c3_dedup_waves_ab.txt, and the routed levels 13 % slower,
+  // profiles/r06_shard_scale_routedup16.txt.)
   static constexpr int kMsgClasses = 1;  // handler classes of messages (Poke); timers: class 1
   static constexpr int kTimerMin = 1, kTimerMax = 100;
   using Rec = uint32_t;

@@ -373,9 +373,7 @@ typedef struct {
   uint64_t exchange_rounds;
   uint64_t fast_levels;
   uint64_t completions;
-  /* successors an earlier successor of the same k_level chunk had already produced (the in-chunk
-     duplicate filter of protocols that enable it): not new, neither probed nor routed */
-  uint64_t deduped;
+  uint64_t deduped; /* reserved, always 0 */
 } dsl_stats;
 
 int dsl_kernel_stats(dsl_engine* e, dsl_stats* out);

@@ -1,7 +1,7 @@
 # A/B of the sharded path's kernels on virtual shards: kernel traces of tools/shard_scale.py for
-# library variants (VARIANTS, beside the product library) and k_materialize grid caps (MATB), then
+# library variants (VARIANTS, beside the product library), then
 # tools/shard_kernels.py per-level summaries. Output: gpurun_out/$TAG/.
-# usage: TAG=x VARIANTS="routeblock" MATB="256 8192" MATP="4 8" WL="multipaxos 12" W=8 bash tools/gpu_shard_ab.sh
+# usage: TAG=x VARIANTS="phases" WL="multipaxos 12" W=8 bash tools/gpu_shard_ab.sh
 set -e
 cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
@@ -20,11 +20,5 @@ run() {  # name, env...
 for v in product $VARIANTS; do
   vv=$v; [ "$v" = product ] && vv=""
   run $v DSL_LIB_VARIANT=$vv
-done
-for m in $MATB; do
-  run matb$m DSL_MAT_BLOCKS=$m
-done
-for m in $MATP; do  # states per wave, grid 4096 workgroups
-  run matp$m DSL_MAT_PER=$m DSL_MAT_BLOCKS=4096
 done
 echo shard ab done

@@ -1,4 +1,5 @@
-# A/B of library variants (DSL_LIB_VARIANT): VARIANTS="pad0 pad1" beside the product library (NOPRODUCT=1: without it),
+# A/B of library variants (DSL_LIB_VARIANT, built by tools/build_variant.sh): VARIANTS="a b" names
+# libdslabs_hip_a.so and libdslabs_hip_b.so, run beside the product library (NOPRODUCT=1: without it),
 # $VN alternating rounds of bench.py --no-cpu-baseline $BENCH_ARGS; then, with PMC=1, one
 # LDS-counter pass per variant (SQ_INSTS_LDS, SQ_LDS_BANK_CONFLICT, SQ_WAVE_CYCLES, SQ_WAIT_ANY).
 set -e

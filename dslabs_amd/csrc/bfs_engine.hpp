@@ -342,10 +342,19 @@ struct BfsEngine : EngineBase {
 
   int state_bytes() const override { return (int)sizeof(typename P::State); }
   int set_settings(const dsl_settings& s) override {
-    int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &dset);
+    DevSettings ds;
+    int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &ds);
     if (rc == DSL_OK) {
+      std::string why;
+      if (!check_field_leaves<P>(ds, &why)) {  // the check that needs P::kNodeWords
+        set_error(why);
+        return DSL_ERR_ARG;  // the engine keeps the settings it had
+      }
+      dset = ds;
       hset = s;
       set_pred_reads<P>(dset, prm);
+      field_leaves = false;
+      for (int i = 0; i < dset.n_ops; i++) field_leaves |= dset.ops[i].id == DSL_PRED_FIELD;
     }
     apply_dropped();
     return rc;
@@ -517,7 +526,7 @@ struct BfsEngine : EngineBase {
   // synthetic C3: 48 VGPRs). The grids and the chunk rounds are sized for it.
   std::vector<std::pair<uint64_t, int>> slot_cache;
   int level_slots(size_t lds, bool route = false) {
-    const uint64_t key = lds * 2 + (route ? 1 : 0);
+    const uint64_t key = lds * 4 + (field_leaves ? 2 : 0) + (route ? 1 : 0);
     for (auto& kv : slot_cache)
       if (kv.first == key) {
         stats.level_slots = std::max(stats.level_slots, kv.second);
@@ -526,14 +535,29 @@ struct BfsEngine : EngineBase {
     int occ = 0, cus = 0, dev = 0;
     (void)hipGetDevice(&dev);
     if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    const hipError_t e = route ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_level<P, true>, kLevelBlock, lds)
-                               : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_level<P, false>, kLevelBlock, lds);
+    const hipError_t e =
+        field_leaves
+            ? (route ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_level<P, true, true>, kLevelBlock, lds)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_level<P, false, true>, kLevelBlock, lds))
+            : (route ? hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_level<P, true>, kLevelBlock, lds)
+                     : hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, k_level<P, false>, kLevelBlock, lds));
     if (e != hipSuccess || occ <= 0) occ = 4;
     (void)hipGetLastError();
     const int slots = std::min(8192, std::max(256, occ * cus));
     slot_cache.push_back({key, slots});
     stats.level_slots = std::max(stats.level_slots, slots);
     return slots;
+  }
+  // The settings hold a generic field leaf (DSL_PRED_FIELD): the searches then launch the kernel
+  // instantiations that judge it (k_level / k_dfs FIELD); every other search launches the ones
+  // without it, whose code is what it was before the leaf existed.
+  bool field_leaves = false;
+  template <bool ROUTE>
+  void launch_level(int grid, size_t lds, const LevelArgs<P>& a) {
+    if (field_leaves)
+      hipLaunchKernelGGL((k_level<P, ROUTE, true>), dim3(grid), dim3(kLevelBlock), lds, stream, a, prm, dset);
+    else
+      hipLaunchKernelGGL((k_level<P, ROUTE, false>), dim3(grid), dim3(kLevelBlock), lds, stream, a, prm, dset);
   }
   int chunk_parents(uint64_t F, bool route = false) {
     const int pb = pb_max();
@@ -631,7 +655,7 @@ struct BfsEngine : EngineBase {
       a.owner_filter = 0;
       if (j == 0) DSL_HIP(hipEventRecord(qev[0], stream));
       const int grid = spread;  // the resident workgroups (the kernel loops over the chunks)
-      hipLaunchKernelGGL((k_level<P, false>), dim3(grid), dim3(kLevelBlock), lds, stream, a, prm, dset);
+      launch_level<false>(grid, lds, a);
       DSL_HIP(hipGetLastError());
     }
     DSL_HIP(hipEventRecord(qev[1], stream));
@@ -825,7 +849,7 @@ struct BfsEngine : EngineBase {
     const uint64_t nchunks = a.segs.chunk0[a.segs.n];
     const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>(nchunks, (uint64_t)slots));
     const size_t lds = (size_t)PB * kRowLds + 16;
-    hipLaunchKernelGGL((k_level<P, false>), dim3(blocks), dim3(kLevelBlock), lds, stream, a, prm, dset);
+    launch_level<false>(blocks, lds, a);
     DSL_HIP(hipGetLastError());
     DSL_HIP(hipMemcpyAsync(out, S.terms, sizeof(TerminalRec), hipMemcpyDeviceToHost, stream));
     DSL_TRY(hsync());
@@ -1974,9 +1998,9 @@ struct BfsEngine : EngineBase {
           const uint64_t nchunks = a.segs.chunk0[a.segs.n];
           const int blocks = (int)std::min<uint64_t>(nchunks, (uint64_t)lslots);
           if (route)
-            hipLaunchKernelGGL((k_level<P, true>), dim3(blocks), dim3(kLevelBlock), lds, stream, a, prm, dset);
+            launch_level<true>(blocks, lds, a);
           else
-            hipLaunchKernelGGL((k_level<P, false>), dim3(blocks), dim3(kLevelBlock), lds, stream, a, prm, dset);
+            launch_level<false>(blocks, lds, a);
           DSL_HIP(hipGetLastError());
         }
         DSL_HIP(hipEventRecord(ev1, stream));
@@ -2504,7 +2528,8 @@ struct BfsEngine : EngineBase {
     }
     const int blocks = (int)((np + kBlock - 1) / kBlock);
     while (true) {
-      hipLaunchKernelGGL(k_dfs<P>, dim3(blocks), dim3(kBlock), 0, stream, a, prm, dset);
+      if (field_leaves) hipLaunchKernelGGL((k_dfs<P, true>), dim3(blocks), dim3(kBlock), 0, stream, a, prm, dset);
+      else hipLaunchKernelGGL((k_dfs<P, false>), dim3(blocks), dim3(kBlock), 0, stream, a, prm, dset);
       DSL_HIP(hipGetLastError());
       DSL_HIP(hipMemcpyAsync(hc, ctr, 24, hipMemcpyDeviceToHost, stream));
       DSL_HIP(hipMemcpyAsync(hf, found, 16, hipMemcpyDeviceToHost, stream));

@@ -32,9 +32,11 @@ struct DevPred {
   int32_t negate;  // leaf: StatePredicate.negate()
   int32_t arg0, arg1;
   uint32_t reads;  // leaf: nodes whose words it reads (bit i = node i; bit 31 = the network)
-  uint32_t pad;
+  uint32_t pad;    // DSL_PRED_FIELD: DSL_CMP_* | kFieldRhsIsField (arg0 = the left field descriptor,
+                   // arg1 = the constant or the right field descriptor, as bit patterns); else 0
 };
 constexpr int32_t kOpAnd = -1, kOpOr = -2, kOpNot = -3;
+constexpr uint32_t kFieldRhsIsField = 8u;
 constexpr uint32_t kReadsAll = 0xffffffffu;
 constexpr int kMaxProgOps = 64;   // ops of all the programs of one search
 constexpr int kMaxProgStack = 16;  // values on a program's stack (2 bits each in one word)

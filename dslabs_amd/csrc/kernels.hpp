@@ -641,7 +641,10 @@ template <class P, class = void>
 struct LevelWaves : std::integral_constant<int, 4> {};
 template <class P>
 struct LevelWaves<P, std::void_t<decltype(P::kLevelWaves)>> : std::integral_constant<int, P::kLevelWaves> {};
-template <class P, bool ROUTE>
+// FIELD: the judge also knows the generic field leaf (DSL_PRED_FIELD). A kernel template switch,
+// launched only for settings that hold such a leaf (BfsEngine::launch_level): the instantiations
+// every other search runs keep the code and the register allocation they had without the leaf.
+template <class P, bool ROUTE, bool FIELD = false>
 __global__ void __launch_bounds__(kLevelBlock) __attribute__((amdgpu_waves_per_eu(LevelWaves<P>::value)))
 k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
   constexpr int NW = Layout<P>::kWords;
@@ -1008,7 +1011,7 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
                 view.sends = ms;
                 view.nsends = dn;
               }
-              const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
+              const int v = judge_view<P, FIELD>(view, prm, set, a.depth, &pi, a.incremental != 0);
               if (v == V_VALID) {
                 if (route) {
                 } else if (Net<P>::size(w) + dn <= P::kNetCap) {
@@ -1880,7 +1883,7 @@ __device__ __forceinline__ uint64_t xorshift64s(uint64_t& x) {
   return x * 0x2545F4914F6CDD1Dull;
 }
 
-template <class P>
+template <class P, bool FIELD = false>  // FIELD: as k_level's
 __global__ void __launch_bounds__(kBlock) k_dfs(DfsArgs a, typename P::Params prm, DevSettings set) {
   constexpr int NW = Layout<P>::kWords;
   const uint64_t lane = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -1922,7 +1925,7 @@ __global__ void __launch_bounds__(kBlock) k_dfs(DfsArgs a, typename P::Params pr
           break;
         } else {
           const NodeView view{nxt, P::kNodeWords, -1, nullptr};
-          v = judge_view<P>(view, prm, set, a.init_depth + dep + 1, &pi);
+          v = judge_view<P, FIELD>(view, prm, set, a.init_depth + dep + 1, &pi);
         }
         if (v >= V_TERM_EXCEPTION) {
           a.trace[lane * a.tcap + dep] = (uint32_t)k;

@@ -16,6 +16,7 @@
 // share a fingerprint is ~ n^2 / 2^129 (each pair of distinct states differs in a non-empty
 // set of hashed components).
 #pragma once
+#include <string>
 #include <type_traits>
 
 #include "common.hpp"
@@ -573,19 +574,56 @@ struct PredSame<P, std::void_t<decltype(&P::pred_same)>> {
   static DSL_HD bool same(const DevPred& pr, const uint32_t* a, const uint32_t* b) { return P::pred_same(pr, a, b); }
 };
 
-template <class P>
+// ---- the generic field leaf (DSL_PRED_FIELD, include/dslabs_hip.h) -------------------------------
+// An unsigned comparison of a bit field of one node with a constant or with a second field,
+// judged here for every protocol (P::eval never sees the id). The word is read with a run-time
+// index through the view's pointers: in every kernel both the parent row and the changed node's
+// words (NodeView::over) are memory (LDS; kernels.hpp copies the delta's words there for the
+// judge), so this is one indexed read, not an index into a per-lane register array.
+DSL_HD uint32_t field_leaf_read(const NodeView& v, uint32_t desc) {
+  const int bit = DSL_FIELD_BIT(desc), width = DSL_FIELD_WIDTH(desc);
+  const uint32_t x = v.node(DSL_FIELD_NODE(desc))[bit >> 5] >> (bit & 31);
+  return width >= 32 ? x : x & ((1u << width) - 1u);  // no 1u << 32
+}
+DSL_HD int eval_field_leaf(const DevPred& pr, const NodeView& v) {
+  const uint32_t a = field_leaf_read(v, (uint32_t)pr.arg0);
+  const uint32_t b = (pr.pad & kFieldRhsIsField) ? field_leaf_read(v, (uint32_t)pr.arg1) : (uint32_t)pr.arg1;
+  // DSL_CMP_*: bits 1-2 pick ==, < or <=; bit 0 negates (NE, GE, GT)
+  const uint32_t c = pr.pad & 7u;
+  const bool base = (c >> 1) == 0 ? a == b : (c >> 1) == 1 ? a < b : a <= b;
+  return (base != (bool)(c & 1u)) ? PV_TRUE : PV_FALSE;
+}
+// Unchanged on the successor: the changed node is not read, or the word holding each field read
+// from it is the same in the old and the new node.
+DSL_HD bool field_leaf_unchanged(const DevPred& pr, const NodeView& v) {
+  if (!((pr.reads >> v.changed) & 1u)) return true;
+  const uint32_t* old = v.base + v.changed * v.nw;
+  const uint32_t l = (uint32_t)pr.arg0, r = (uint32_t)pr.arg1;
+  uint32_t d = 0;
+  if (DSL_FIELD_NODE(l) == v.changed) d |= old[DSL_FIELD_BIT(l) >> 5] ^ v.over[DSL_FIELD_BIT(l) >> 5];
+  if ((pr.pad & kFieldRhsIsField) && DSL_FIELD_NODE(r) == v.changed)
+    d |= old[DSL_FIELD_BIT(r) >> 5] ^ v.over[DSL_FIELD_BIT(r) >> 5];
+  return d == 0;
+}
+
+// kField (here and below): the judge knows the field leaf. Host code always does; a kernel is
+// instantiated without it for the searches whose settings hold none (kernels.hpp: FIELD).
+template <class P, bool kField = true>
 DSL_HD bool leaf_unchanged(const DevPred& pr, const NodeView& v) {
+  if constexpr (kField) {
+    if (pr.id == DSL_PRED_FIELD) return field_leaf_unchanged(pr, v);
+  }
   if (pr.reads >> 31) return false;
   if (!((pr.reads >> v.changed) & 1u)) return true;
   return PredSame<P>::same(pr, v.base + v.changed * v.nw, v.over);
 }
 // A program is unchanged when every leaf is.
-template <class P>
+template <class P, bool kField = true>
 DSL_HD bool prog_unchanged(const DevSettings& set, DevProg g, const NodeView& v, bool incremental) {
   if (!incremental || v.changed < 0) return false;
   for (int i = 0; i < g.len; i++) {
     const DevPred& op = set.ops[g.start + i];
-    if (op.id > 0 && !leaf_unchanged<P>(op, v)) return false;
+    if (op.id > 0 && !leaf_unchanged<P, kField>(op, v)) return false;
   }
   return true;
 }
@@ -594,7 +632,7 @@ DSL_HD bool prog_unchanged(const DevSettings& set, DevProg g, const NodeView& v,
 // kept in one word (no indexed private array). Combinators follow StatePredicate.java:397-431: a
 // throwing left operand throws; and(a, b) is a when a is false, else b; or(a, b) is a when a is
 // true, else b; negate keeps a throw.
-template <class P>
+template <class P, bool kField = true>
 DSL_HD int eval_prog(const DevSettings& set, DevProg g, const NodeView& v, const typename P::Params& prm) {
   uint32_t st = 0;
   for (int i = 0; i < g.len; i++) {
@@ -611,7 +649,11 @@ DSL_HD int eval_prog(const DevSettings& set, DevProg g, const NodeView& v, const
       st >>= 2;
       x = a == PV_THREW ? PV_THREW : !a;
     } else {
-      x = P::eval(op, v, prm);
+      if constexpr (kField) {
+        x = op.id == DSL_PRED_FIELD ? eval_field_leaf(op, v) : P::eval(op, v, prm);
+      } else {
+        x = P::eval(op, v, prm);
+      }
       if (x != PV_THREW && op.negate) x = !x;
     }
     st = (st << 2) | (uint32_t)x;
@@ -649,7 +691,7 @@ struct EvalHeld<P, std::void_t<decltype(&P::eval_held)>> {
 // The invariants, goals and prunes are walked as ONE sequence (programs [0, n_inv) are the
 // invariants, then the goals, then the prunes), so the protocol's predicate code is inlined once
 // rather than once per kind.
-template <class P>
+template <class P, bool kField = true>
 DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, const DevSettings& set, int depth,
                           int* pred_index, bool incremental = false) {
   NodeView v = v0;
@@ -663,8 +705,15 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
     // (invariants, goals, prunes) -- no program descriptors, no stack machine
     for (int t = 0; t < nt; t++) {
       const DevPred& op = set.ops[t];
-      if (incremental && v.changed >= 0 && leaf_unchanged<P>(op, v)) continue;
-      int x = EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
+      if (incremental && v.changed >= 0 && leaf_unchanged<P, kField>(op, v)) continue;
+      int x;
+      if constexpr (kField) {
+        x = op.id == DSL_PRED_FIELD
+                ? eval_field_leaf(op, v)
+                : EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
+      } else {
+        x = EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
+      }
       if (x != PV_THREW && op.negate) x = !x;
       if (t < set.n_inv) {
         if (x != PV_TRUE) {  // a false or throwing invariant is violated
@@ -687,8 +736,8 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
     const int kind = t < set.n_inv ? 0 : t < ng ? 1 : 2;
     const int i = kind == 0 ? t : kind == 1 ? t - set.n_inv : t - ng;
     const DevProg g = kind == 0 ? set.inv[i] : kind == 1 ? set.goal[i] : set.prune[i];
-    if (prog_unchanged<P>(set, g, v, incremental)) continue;
-    const int x = eval_prog<P>(set, g, v, prm);
+    if (prog_unchanged<P, kField>(set, g, v, incremental)) continue;
+    const int x = eval_prog<P, kField>(set, g, v, prm);
     if (kind == 0 && x != PV_TRUE) {  // a false or throwing invariant is violated
       *pred_index = i;
       return V_TERM_INVARIANT;
@@ -704,10 +753,40 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
 }
 
 // Fills DevPred::reads of every leaf from the protocol's read sets (host, after resolve_settings).
+// A field leaf reads exactly its node, or its two nodes (the protocol is not asked: it would
+// answer kReadsAll for an id it does not know).
 template <class P>
 void set_pred_reads(DevSettings& d, const typename P::Params& prm) {
-  for (int i = 0; i < d.n_ops; i++)
-    if (d.ops[i].id > 0) d.ops[i].reads = P::pred_reads(d.ops[i], prm);
+  for (int i = 0; i < d.n_ops; i++) {
+    DevPred& op = d.ops[i];
+    if (op.id == DSL_PRED_FIELD) {
+      op.reads = 1u << DSL_FIELD_NODE((uint32_t)op.arg0);
+      if (op.pad & kFieldRhsIsField) op.reads |= 1u << DSL_FIELD_NODE((uint32_t)op.arg1);
+    } else if (op.id > 0) {
+      op.reads = P::pred_reads(op, prm);
+    }
+  }
+}
+
+// The one check of a field leaf that needs the protocol: the field lies inside the node's words
+// (resolve_settings checked the rest). Host; false with the fault named in *why.
+template <class P>
+bool check_field_leaves(const DevSettings& d, std::string* why) {
+  for (int i = 0; i < d.n_ops; i++) {
+    const DevPred& op = d.ops[i];
+    if (op.id != DSL_PRED_FIELD) continue;
+    const uint32_t descs[2] = {(uint32_t)op.arg0, (uint32_t)op.arg1};
+    for (int k = 0; k < ((op.pad & kFieldRhsIsField) ? 2 : 1); k++) {
+      const int bit = DSL_FIELD_BIT(descs[k]), width = DSL_FIELD_WIDTH(descs[k]);
+      if (bit + width > 32 * P::kNodeWords) {
+        *why = std::string("field predicate: ") + (k ? "right" : "left") + " operand (node " +
+               std::to_string(DSL_FIELD_NODE(descs[k])) + ", bit " + std::to_string(bit) + ", width " +
+               std::to_string(width) + "): beyond the node's " + std::to_string(32 * P::kNodeWords) + " bits";
+        return false;
+      }
+    }
+  }
+  return true;
 }
 
 }  // namespace dsl

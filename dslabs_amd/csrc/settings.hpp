@@ -67,6 +67,33 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
       if (p.negate && !push_op(kOpNot)) return false;
       return true;
     }
+    if (p.pred_id == DSL_PRED_FIELD) {
+      // the generic field leaf: every protocol's (the judge evaluates it, not P::eval); packed
+      // into the DevPred's 96 argument bits. The one check that needs the protocol's words per
+      // node is check_field_leaves<P> (nodestate.hpp), where P is known.
+      const uint64_t a0 = (uint64_t)p.arg0, a1 = (uint64_t)p.arg1;
+      const int cmp = DSL_FIELD_ARG0_CMP(a0), rhs_field = DSL_FIELD_ARG0_RHS_IS_FIELD(a0);
+      if (a0 >> 36) return why = "field predicate: arg0 has bits set above the descriptor, comparison and operand kind", false;
+      if (cmp > DSL_CMP_GT) return why = "field predicate: unknown comparison " + std::to_string(cmp), false;
+      if (a1 >> 32) return why = "field predicate: arg1 does not fit in 32 unsigned bits", false;
+      auto bad_desc = [&](uint32_t desc, const char* side) {
+        const int node = DSL_FIELD_NODE(desc), bit = DSL_FIELD_BIT(desc), width = DSL_FIELD_WIDTH(desc);
+        const std::string at = std::string("field predicate: ") + side + " operand (node " + std::to_string(node) +
+                               ", bit " + std::to_string(bit) + ", width " + std::to_string(width) + "): ";
+        if (desc & ~DSL_FIELD_DESC_MASK) return why = at + "descriptor has bits set above bit 26", true;
+        if (node >= num_nodes) return why = at + "node index >= the protocol's " + std::to_string(num_nodes) + " nodes", true;
+        if (width < 1 || width > 32) return why = at + "width outside 1..32", true;
+        if ((bit & 31) + width > 32) return why = at + "field straddles a 32-bit word", true;
+        return false;
+      };
+      if (bad_desc(DSL_FIELD_ARG0_DESC(a0), "left")) return false;
+      if (rhs_field && bad_desc((uint32_t)a1, "right")) return false;
+      if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
+      d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, (int32_t)DSL_FIELD_ARG0_DESC(a0), (int32_t)(uint32_t)a1, 0u,
+                                 (uint32_t)cmp | (rhs_field ? kFieldRhsIsField : 0u)};
+      if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
+      return true;
+    }
     if (!known(p.pred_id)) return why = "predicate not supported by this protocol's device predicates", false;
     if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
     d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, (int32_t)p.arg0, (int32_t)p.arg1, 0u, 0u};

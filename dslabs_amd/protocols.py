@@ -52,12 +52,25 @@ class Protocol:
     def initial_state(self) -> SearchState:
         return SearchState(self)
 
+    # 32-bit words per node of the packed state (the device protocol's kNodeWords)
+    node_words = 0
+
+    def raw_field(self, address, bit: int, width: int):
+        """``width`` bits (1..32, inside one 32-bit word) from bit ``bit`` of ``address``'s node
+        words, for a caller who knows the packed layout (csrc/protocols/*.hpp): a FieldRef to
+        compare (``.lt(3)``, ``== other``, ...) into a StatePredicate judged on the device."""
+        from .search import make_field_ref
+        name = address if isinstance(address, str) else self.addresses[address] if \
+            isinstance(address, int) and 0 <= address < len(self.addresses) else repr(address)
+        return make_field_ref(self, address, bit, width, f"{name}.bits[{bit}:{bit + width}]")
+
 
 class PingPong(Protocol):
     """lab0 PingPong: 1 server ("pingserver"), ``clients`` ClientWorkers with
     ``repeatedPings(pings)`` (labs/lab0-pingpong/tst/dslabs/pingpong/PingTest.java:44-51)."""
 
     proto_id = DSL_PROTO_PINGPONG
+    node_words = 5
 
     def __init__(self, clients: int = 1, pings: int = 10, check_value: bool = True, reset_timer: bool = True):
         self.clients = clients
@@ -87,6 +100,7 @@ class SIPaxos(Protocol):
     "proposer1..P" with initial values, acceptors "acceptor1..A"."""
 
     proto_id = DSL_PROTO_SIPAXOS
+    node_words = 3
     PREDICATES = {"Agreement": 100, "Integrity": 101, "Termination": 102}
 
     def __init__(self, proposers: int = 2, acceptors: int = 3, values=("a", "b"), incorrect: bool = False):
@@ -127,6 +141,7 @@ class MultiPaxos(Protocol):
     tokens, <= 4 per value); result codes: 7 PutOk, 6 KeyNotFound, else a value."""
 
     proto_id = DSL_PROTO_MULTIPAXOS
+    node_words = 6
     PREDICATES = {"LOGS_CONSISTENT_ALL_SLOTS": (400, "Non-empty log slots consistent"),
                   "LOGS_CONSISTENT": (401, "Active log slots consistent"),
                   "APPENDS_LINEARIZABLE": (300, "Sequence of appends to the same key is linearizable")}
@@ -291,6 +306,7 @@ class Synthetic(Protocol):
     state, ~20-25 enabled events per state: a dedup / all-to-all stress test."""
 
     proto_id = DSL_PROTO_SYNTHETIC
+    node_words = 2
     SEED = 0x5EEDD51AB5
 
     def __init__(self, nodes: int = 5, values: int = 64, poke_mod: int = 7, seed: int = SEED):
@@ -325,6 +341,7 @@ class AmoKV(Protocol):
     (labs/lab1-clientserver/tst/dslabs/kvstore/KVStoreWorkload.java, ClientServerPart2Test.java)."""
 
     proto_id = DSL_PROTO_AMOKV
+    node_words = 6
     PREDICATES = {"APPENDS_LINEARIZABLE": (300, "Sequence of appends to the same key is linearizable")}
     # same names and templates as oracle/proto_amokv.hpp (commands, results, numTimes)
     WORKLOADS = {
@@ -434,6 +451,7 @@ class PB(Protocol):
     lab1 (PrimaryBackupTest uses putGetWorkload, PrimaryBackupTest.java:680-711)."""
 
     proto_id = DSL_PROTO_PB
+    node_words = 3
     WORKLOADS = dict(AmoKV.WORKLOADS, putget=(["PUT:foo:bar", "GET:foo"], ["Ok", "bar"], 1))
     RTYPES = AmoKV.RTYPES
 
@@ -618,6 +636,7 @@ class MiniTest(Protocol):
     ``alwaysException`` (:104-126, :255-260)."""
 
     proto_id = DSL_PROTO_MINITEST
+    node_words = 1
 
     def __init__(self):
         self.addresses = ["a", "b"]
@@ -663,6 +682,53 @@ class IRProtocol(Protocol):
 
     def params(self):
         return [self.values[p.name] for p in self.spec.params]
+
+    # ---- named fields (FieldRef), resolved from the spec's layout --------------------------------
+    @property
+    def node_words(self) -> int:
+        self.spec.layout()
+        return self.spec.node_words
+
+    def _field_decl(self, address, name: str):
+        """(node kind, FieldDecl) of field ``name`` of ``address``'s node."""
+        self.spec.layout()
+        node = self.address_index(address)
+        first = 0
+        for k in self.spec.kinds:  # kinds in declaration order, instances consecutive (this run's counts)
+            n = self.spec.count_of(k, self.values)
+            if first <= node < first + n:
+                for f in k.fields:
+                    if f.name == name:
+                        return k, f
+                raise ValueError(f"{self.addresses[node]} (a {k.name}) has no field {name!r}")
+            first += n
+        raise ValueError(f"unknown address {address!r}")
+
+    def field(self, address, name: str, j=None):
+        """Field ``name`` of ``address``'s node, or element ``j`` (a constant, from 0) of a list or
+        array field, as a FieldRef: ``proto.field("server2", "round") <= 3``."""
+        from .search import make_field_ref
+        _, f = self._field_decl(address, name)
+        label = f"{self.addresses[self.address_index(address)]}.{name}"
+        if not f.cap:
+            if j is not None:
+                raise ValueError(f"{label} is a scalar field: no index")
+            return make_field_ref(self, address, f.off, f.bits, label)
+        if j is None:
+            raise ValueError(f"{label} is a list of {f.cap}: give an element index (or use length())")
+        if isinstance(j, bool) or not isinstance(j, int) or not 0 <= j < f.cap:
+            raise ValueError(f"{label}[{j}]: index outside 0..{f.cap - 1}")
+        return make_field_ref(self, address, f.off + (j // f.per) * 32 + (j % f.per) * f.bits, f.bits, f"{label}[{j}]")
+
+    def length(self, address, name: str):
+        """The length of a bounded list field, the implicit ``_results`` (a client's harvested
+        results) and ``_timers`` (where the kind keeps a timer queue) included, as a FieldRef."""
+        from .search import make_field_ref
+        _, f = self._field_decl(address, name)
+        label = f"{self.addresses[self.address_index(address)]}.{name}"
+        if not f.cap or f.array:
+            raise ValueError(f"{label} is not a bounded list: it has no length")
+        return make_field_ref(self, address, f.len_off, f.len_bits, f"length({label})")
 
     def render_event(self, e) -> str:
         a = self.addresses

@@ -45,6 +45,32 @@ PRED_OR = 901
 PRED_IMPLIES = 902
 
 
+# the generic field leaf (DSL_PRED_FIELD) and its comparisons (DSL_CMP_*, include/dslabs_hip.h)
+PRED_FIELD = 950
+CMP_EQ, CMP_NE, CMP_LT, CMP_GE, CMP_LE, CMP_GT = 0, 1, 2, 3, 4, 5
+_CMP_TEXT = {CMP_EQ: "==", CMP_NE: "!=", CMP_LT: "<", CMP_GE: ">=", CMP_LE: "<=", CMP_GT: ">"}
+
+
+def field_desc(node: int, bit: int, width: int) -> int:
+    """DSL_FIELD_DESC: bit (bits 0-15) | width << 16 (bits 16-21) | node << 22 (bits 22-26)."""
+    return (node << 22) | (width << 16) | bit
+
+
+def field_desc_decode(desc: int) -> tuple:
+    """(node, bit, width) of a descriptor (DSL_FIELD_NODE / _BIT / _WIDTH)."""
+    return (desc >> 22) & 0x1F, desc & 0xFFFF, (desc >> 16) & 0x3F
+
+
+def field_arg0(desc: int, cmp: int, rhs_is_field: bool) -> int:
+    """DSL_FIELD_ARG0: descriptor | comparison << 32 | (right operand is a field) << 35."""
+    return desc | (cmp << 32) | ((1 if rhs_is_field else 0) << 35)
+
+
+def field_arg0_decode(arg0: int) -> tuple:
+    """(descriptor, comparison, rhs_is_field) of a field leaf's arg0."""
+    return arg0 & 0xFFFFFFFF, (arg0 >> 32) & 7, bool((arg0 >> 35) & 1)
+
+
 class StatePredicate:
     """A named state predicate evaluated on the device (StatePredicate.java).
 
@@ -111,6 +137,120 @@ def clientDone(address: str) -> StatePredicate:
 def clientHasResults(address: str, numResults: int) -> StatePredicate:
     return StatePredicate(f"{address} received {numResults} results", PRED_CLIENT_HAS_RESULTS, address,
                           numResults, address_args=(0,))
+
+
+class FieldRef:
+    """``width`` bits from bit ``bit`` of one node's packed words: a named field of a protocol's
+    node (``IRProtocol.field`` / ``length``), a part of one (``bits``), or a raw bit range
+    (``Protocol.raw_field``). Comparing it with an int or with another FieldRef (``eq / ne / lt /
+    le / gt / ge`` or the operators; unsigned) gives a StatePredicate the engine judges on the
+    device: the user-written predicate of StatePredicate.statePredicate (StatePredicate.java:168-176)."""
+
+    def __init__(self, protocol, node: int, bit: int, width: int, name: str):
+        self.protocol, self.node, self.bit, self.width, self.name = protocol, node, bit, width, name
+
+    def desc(self) -> int:
+        return field_desc(self.node, self.bit, self.width)
+
+    def bits(self, lo: int, width: int) -> "FieldRef":
+        """The sub-field of ``width`` bits from bit ``lo`` of this field."""
+        if lo < 0 or width < 1 or lo + width > self.width:
+            raise ValueError(f"bits({lo}, {width}) outside {self.name} ({self.width} bits)")
+        return FieldRef(self.protocol, self.node, self.bit + lo, width, f"{self.name}[{lo}:{lo + width}]")
+
+    def _cmp(self, cmp: int, other) -> StatePredicate:
+        if isinstance(other, FieldRef):
+            if other.protocol is not self.protocol:
+                raise ValueError(f"{self.name} and {other.name} belong to different protocol objects")
+            return StatePredicate(f"{self.name} {_CMP_TEXT[cmp]} {other.name}", PRED_FIELD,
+                                  field_arg0(self.desc(), cmp, True), other.desc())
+        if isinstance(other, bool) or not isinstance(other, int):
+            raise TypeError(f"{self.name}: compare with an int or a FieldRef, not {type(other).__name__}")
+        if other < 0 or other >= 1 << 32:
+            raise ValueError(f"{self.name}: constant {other} does not fit in 32 unsigned bits")
+        return StatePredicate(f"{self.name} {_CMP_TEXT[cmp]} {other}", PRED_FIELD,
+                              field_arg0(self.desc(), cmp, False), other)
+
+    def eq(self, other) -> StatePredicate:
+        return self._cmp(CMP_EQ, other)
+
+    def ne(self, other) -> StatePredicate:
+        return self._cmp(CMP_NE, other)
+
+    def lt(self, other) -> StatePredicate:
+        return self._cmp(CMP_LT, other)
+
+    def le(self, other) -> StatePredicate:
+        return self._cmp(CMP_LE, other)
+
+    def gt(self, other) -> StatePredicate:
+        return self._cmp(CMP_GT, other)
+
+    def ge(self, other) -> StatePredicate:
+        return self._cmp(CMP_GE, other)
+
+    __eq__, __ne__, __lt__, __le__, __gt__, __ge__ = eq, ne, lt, le, gt, ge
+    __hash__ = object.__hash__
+
+    def __repr__(self) -> str:
+        return self.name
+
+
+def make_field_ref(protocol, address, bit: int, width: int, name: str) -> FieldRef:
+    """A checked FieldRef: a known address, 1..32 bits inside one 32-bit word and (where the
+    protocol's words per node are known: ``protocol.node_words``) inside the node."""
+    node = protocol.address_index(address)
+    if not 0 <= node < len(protocol.addresses):
+        raise ValueError(f"unknown address {address!r}")
+    if not 1 <= width <= 32:
+        raise ValueError(f"{name}: width {width} outside 1..32")
+    if bit < 0 or bit >= 1 << 16:
+        raise ValueError(f"{name}: bit {bit} outside the node")
+    if (bit & 31) + width > 32:
+        raise ValueError(f"{name}: bits {bit}..{bit + width - 1} straddle a 32-bit word")
+    nw = getattr(protocol, "node_words", 0)
+    if nw and bit + width > 32 * nw:
+        raise ValueError(f"{name}: bits {bit}..{bit + width - 1} beyond the node's {32 * nw} bits")
+    return FieldRef(protocol, node, bit, width, name)
+
+
+def statePredicate(name: str, pred: StatePredicate) -> StatePredicate:
+    """StatePredicate.statePredicate(name, fn) (StatePredicate.java:168-176) for a predicate built
+    from field comparisons and combinators: the same predicate under ``name``."""
+    return StatePredicate(name, pred.pred_id, pred.arg0, pred.arg1, pred.negated, pred.address_args, pred.operands)
+
+
+def _fold(preds, op: str, what: str) -> StatePredicate:
+    preds = list(preds)
+    if not preds:
+        raise ValueError(f"{what} of no predicates")
+    out = preds[0]
+    for p in preds[1:]:
+        out = getattr(out, op)(p)
+    return out
+
+
+def allOf(preds) -> StatePredicate:
+    """The conjunction of a non-empty list, folded left with ``and_``."""
+    return _fold(preds, "and_", "allOf")
+
+
+def anyOf(preds) -> StatePredicate:
+    """The disjunction of a non-empty list, folded left with ``or_``."""
+    return _fold(preds, "or_", "anyOf")
+
+
+def field_value(state: "SearchState", ref: FieldRef) -> int:
+    """The value of ``ref`` in a state's packed bytes (node i is words [i * node_words,
+    (i + 1) * node_words) of the row, little-endian 32-bit words): what the device's field leaf
+    reads, decoded on the host."""
+    nw = getattr(state.protocol, "node_words", 0)
+    if not nw:
+        raise ValueError(f"{type(state.protocol).__name__} does not declare node_words")
+    packed = state._packed_now()
+    w = (ref.node * nw + (ref.bit >> 5)) * 4
+    word = int.from_bytes(packed[w:w + 4], "little")
+    return (word >> (ref.bit & 31)) & ((1 << ref.width) - 1)
 
 
 @dataclass

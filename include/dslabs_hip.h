@@ -40,7 +40,9 @@ extern "C" {
                                dsl_stats exchange_rounds / fast_levels / completions;
                             5: dsl_stats deduped;
                             6: dsl_settings.max_terminals, dsl_result terminals_total / n_terminals /
-                               terminals, dsl_terminal */
+                               terminals, dsl_terminal.
+                            Still 6 with DSL_PRED_FIELD: a new dsl_predicate_id changes no struct and adds
+                            no entry point; a library without it answers DSL_ERR_UNKNOWN_PREDICATE */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -126,8 +128,41 @@ typedef enum {
    * is false, else b; or(a, b) is a when a is true, else b; implies(a, b) = or(negate(a), b). */
   DSL_PRED_AND = 900,
   DSL_PRED_OR = 901,
-  DSL_PRED_IMPLIES = 902
+  DSL_PRED_IMPLIES = 902,
+  /* The generic field leaf (StatePredicate.statePredicate(name, fn), T/StatePredicate.java:168-176,
+   * for fn = a comparison over node fields): an unsigned comparison of a bit field of one node's
+   * words with a constant or with a second bit field. Every protocol accepts it; it never throws;
+   * negate applies as for any leaf and it may be an operand of the combinators. Encoding below
+   * (DSL_FIELD_*). A bad descriptor is refused by dsl_set_settings with DSL_ERR_ARG. */
+  DSL_PRED_FIELD = 950
 } dsl_predicate_id;
+
+/* DSL_PRED_FIELD. A field descriptor (27 bits) names `width` bits (1..32) from bit `bit` of node
+ * `node`'s words (bit 0 = the least significant bit of the node's word 0; the field lies inside
+ * one 32-bit word: (bit % 32) + width <= 32, and inside the node: bit + width <= 32 * the
+ * protocol's words per node):
+ *     descriptor = bit (bits 0-15) | width << 16 (bits 16-21) | node << 22 (bits 22-26)
+ * dsl_predicate.arg0 = left descriptor (bits 0-31) | comparison << 32 (bits 32-34)
+ *                      | (right operand is a field) << 35; every other bit 0
+ * dsl_predicate.arg1 = an unsigned constant 0 .. 2^32-1, or the right operand's descriptor
+ * The predicate is  left <comparison> right  over the unsigned field values. */
+#define DSL_CMP_EQ 0
+#define DSL_CMP_NE 1
+#define DSL_CMP_LT 2
+#define DSL_CMP_GE 3
+#define DSL_CMP_LE 4
+#define DSL_CMP_GT 5
+#define DSL_FIELD_DESC(node, bit, width) \
+  (((uint32_t)(node) << 22) | ((uint32_t)(width) << 16) | (uint32_t)(bit))
+#define DSL_FIELD_BIT(desc) ((int)((uint32_t)(desc) & 0xffffu))
+#define DSL_FIELD_WIDTH(desc) ((int)(((uint32_t)(desc) >> 16) & 0x3fu))
+#define DSL_FIELD_NODE(desc) ((int)(((uint32_t)(desc) >> 22) & 0x1fu))
+#define DSL_FIELD_DESC_MASK 0x07ffffffu
+#define DSL_FIELD_ARG0(desc, cmp, rhs_is_field) \
+  ((int64_t)(uint32_t)(desc) | ((int64_t)(cmp) << 32) | ((int64_t)((rhs_is_field) ? 1 : 0) << 35))
+#define DSL_FIELD_ARG0_DESC(arg0) ((uint32_t)((uint64_t)(arg0) & 0xffffffffu))
+#define DSL_FIELD_ARG0_CMP(arg0) ((int)(((uint64_t)(arg0) >> 32) & 7u))
+#define DSL_FIELD_ARG0_RHS_IS_FIELD(arg0) ((int)(((uint64_t)(arg0) >> 35) & 1u))
 
 typedef struct {
   int32_t pred_id;   /* dsl_predicate_id */

@@ -27,6 +27,25 @@ public final class GpuPredicates {
   /** A predicate leaf on the device: id and two integer arguments. */
   public record Leaf(int id, long arg0, long arg1) {}
 
+  /** DSL_PRED_FIELD and its comparisons (DSL_CMP_*): a leaf every protocol accepts. */
+  public static final int FIELD = 950;
+  public static final int CMP_EQ = 0, CMP_NE = 1, CMP_LT = 2, CMP_GE = 3, CMP_LE = 4, CMP_GT = 5;
+
+  /** DSL_FIELD_DESC: width bits (1..32, inside one 32-bit word) from bit `bit` of node `node`'s words. */
+  public static long fieldDesc(int node, int bit, int width) {
+    return ((long) node << 22) | ((long) width << 16) | bit;
+  }
+
+  /** The field (a descriptor) compared, unsigned, with a constant 0 .. 2^32-1. */
+  public static Leaf field(long desc, int cmp, long constant) {
+    return new Leaf(FIELD, desc | ((long) cmp << 32), constant);
+  }
+
+  /** The field compared with a second field. */
+  public static Leaf fieldField(long desc, int cmp, long otherDesc) {
+    return new Leaf(FIELD, desc | ((long) cmp << 32) | (1L << 35), otherDesc);
+  }
+
   private record Tree(int id, boolean negate, long arg0, long arg1, Tree left, Tree right) {}
 
   private GpuPredicates() {}

@@ -346,7 +346,7 @@ struct BfsEngine : EngineBase {
     int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &ds);
     if (rc == DSL_OK) {
       std::string why;
-      if (!check_field_leaves<P>(ds, &why)) {  // the check that needs P::kNodeWords
+      if (!check_field_leaves<P>(ds, &why) || !check_net_leaves<P>(ds, &why)) {  // the checks that need P
         set_error(why);
         return DSL_ERR_ARG;  // the engine keeps the settings it had
       }
@@ -354,7 +354,7 @@ struct BfsEngine : EngineBase {
       hset = s;
       set_pred_reads<P>(dset, prm);
       field_leaves = false;
-      for (int i = 0; i < dset.n_ops; i++) field_leaves |= dset.ops[i].id == DSL_PRED_FIELD;
+      for (int i = 0; i < dset.n_ops; i++) field_leaves |= dset.ops[i].id == DSL_PRED_FIELD || dset.ops[i].id == DSL_PRED_NET;
     }
     apply_dropped();
     return rc;
@@ -373,7 +373,7 @@ struct BfsEngine : EngineBase {
     if (n < 0 || (n > 0 && !recs)) return DSL_ERR_ARG;
     dropped_h.assign(n, typename P::Rec{});
     for (int i = 0; i < n; i++) dropped_h[i] = (typename P::Rec)recs[i];
-    if (n > 0 && NetPreds<P>::value) {
+    if (n > 0) {  // every protocol: the generic network leaf (DSL_PRED_NET) reads them in the kernels
       if (cfg.device >= 0) DSL_HIP(hipSetDevice(cfg.device));
       DSL_TRY(grow(&dropped_d, &dropped_cap, (uint64_t)n, false, 0));
       DSL_HIP(hipMemcpy(dropped_d, dropped_h.data(), n * sizeof(typename P::Rec), hipMemcpyHostToDevice));
@@ -548,7 +548,7 @@ struct BfsEngine : EngineBase {
     stats.level_slots = std::max(stats.level_slots, slots);
     return slots;
   }
-  // The settings hold a generic field leaf (DSL_PRED_FIELD): the searches then launch the kernel
+  // The settings hold a generic leaf (DSL_PRED_FIELD or DSL_PRED_NET): the searches then launch the kernel
   // instantiations that judge it (k_level / k_dfs FIELD); every other search launches the ones
   // without it, whose code is what it was before the leaf existed.
   bool field_leaves = false;

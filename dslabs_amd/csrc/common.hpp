@@ -33,8 +33,19 @@ struct DevPred {
   int32_t arg0, arg1;
   uint32_t reads;  // leaf: nodes whose words it reads (bit i = node i; bit 31 = the network)
   uint32_t pad;    // DSL_PRED_FIELD: DSL_CMP_* | kFieldRhsIsField (arg0 = the left field descriptor,
-                   // arg1 = the constant or the right field descriptor, as bit patterns); else 0
+                   // arg1 = the constant or the right field descriptor, as bit patterns);
+                   // DSL_PRED_NET: the leaf's ordinal among the settings' network leaves (its bit in
+                   // NodeView::net_hits; arg0 = its first DevSettings::rec_conds entry, arg1 = how
+                   // many); else 0
 };
+// One condition of a network leaf (DSL_PRED_REC_COND): (record >> bit) & mask(width) <cmp> k.
+struct DevRecCond {
+  uint16_t bit;
+  uint8_t width;  // 1..32
+  uint8_t cmp;    // DSL_CMP_*
+  uint32_t k;
+};
+constexpr int kMaxRecConds = DSL_MAX_NET_CONDS_TOTAL;
 constexpr int32_t kOpAnd = -1, kOpOr = -2, kOpNot = -3;
 constexpr uint32_t kFieldRhsIsField = 8u;
 constexpr uint32_t kReadsAll = 0xffffffffu;
@@ -59,7 +70,7 @@ struct DevSettings {
   // -- invariants, goals, prunes (resolve_settings emits them in that order); judge_view then walks
   // the leaves directly (no program descriptors, no stack)
   int32_t flat;
-  int32_t pad_flat;
+  int32_t n_net;  // network leaves (DSL_PRED_NET) among ops[]; each has a bit of NodeView::net_hits
   DevProg inv[DSL_MAX_PREDICATES];
   DevProg goal[DSL_MAX_PREDICATES];
   DevProg prune[DSL_MAX_PREDICATES];
@@ -78,6 +89,9 @@ struct DevSettings {
     return dropped_host;
 #endif
   }
+  // the conditions of the network leaves (behind everything else: the offsets of the fields the
+  // kernels without the leaf read are what they were)
+  DevRecCond rec_conds[kMaxRecConds];
 };
 
 // True when no active lane of the wavefront has `p` (device; one thread on the host): the exit of

@@ -641,8 +641,8 @@ template <class P, class = void>
 struct LevelWaves : std::integral_constant<int, 4> {};
 template <class P>
 struct LevelWaves<P, std::void_t<decltype(P::kLevelWaves)>> : std::integral_constant<int, P::kLevelWaves> {};
-// FIELD: the judge also knows the generic field leaf (DSL_PRED_FIELD). A kernel template switch,
-// launched only for settings that hold such a leaf (BfsEngine::launch_level): the instantiations
+// FIELD: the judge also knows the generic leaves (DSL_PRED_FIELD, DSL_PRED_NET). A kernel template
+// switch, launched only for settings that hold such a leaf (BfsEngine::launch_level): the instantiations
 // every other search runs keep the code and the register allocation they had without the leaf.
 template <class P, bool ROUTE, bool FIELD = false>
 __global__ void __launch_bounds__(kLevelBlock) __attribute__((amdgpu_waves_per_eu(LevelWaves<P>::value)))
@@ -951,6 +951,12 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
           uint32_t* my_nw = s_nodew + tid * P::kNodeWords;  // the changed node's words, for the judge
           int rc, dnode = 0, dn = 0;
           bool noop = false;
+          // the network leaves' scan of the parent row, where the judge will ask for it (never on
+          // the common path, net_needs_row): here, ahead of the handler, few registers are live
+          uint32_t row_hits = 0;
+          if constexpr (FIELD) {
+            if (net_needs_row(set, a.incremental != 0, 0)) row_hits = row_net_hits<P>(set, w);
+          }
           // an event that changes neither its node nor the network (a redelivered message most
           // often) leads back to the parent, which is in the visited set: no probe
           {
@@ -1010,6 +1016,10 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
                   if ((d.keep >> q) & 1u) ms[c++] = d.out.r[q];
                 view.sends = ms;
                 view.nsends = dn;
+              }
+              if constexpr (FIELD) {  // the network leaves' hit mask, from the send list's registers
+                if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
+                view.row_hits = row_hits;
               }
               const int v = judge_view<P, FIELD>(view, prm, set, a.depth, &pi, a.incremental != 0);
               if (v == V_VALID) {
@@ -1626,6 +1636,8 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
     d.out.n = 0;
     d.keep = 0;
     Fp f{0, 0};
+    uint32_t row_hits = 0;  // as k_level's: the network leaves' scan of the parent row, ahead of the handler
+    if (act && net_needs_row(set, a.incremental != 0, 0)) row_hits = row_net_hits<P>(set, w);
     if (act) {
       delta_step<P>(w, k, d, prm, set);  // deterministic: the successor k_level fingerprinted
     }
@@ -1648,6 +1660,8 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
         view.sends = ms;
         view.nsends = c;
       }
+      if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
+      view.row_hits = row_hits;
       const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
       if (v == V_VALID) {
         if (Net<P>::size(w) + delta_new_count<P>(d) <= P::kNetCap) ship = true;
@@ -1785,6 +1799,8 @@ __global__ void __launch_bounds__(kBlock) k_list_terminals(ListArgs<P> a, typena
         d.node = 0;
         d.out.n = 0;
         d.keep = 0;
+        uint32_t row_hits = 0;  // as k_level's
+        if (net_needs_row(set, a.incremental != 0, 0)) row_hits = row_net_hits<P>(set, w);
         const int rc = delta_step<P>(w, k, d, prm, set);
         if (rc == STEP_OK) {
           const int dn = delta_new_count<P>(d);
@@ -1807,6 +1823,8 @@ __global__ void __launch_bounds__(kBlock) k_list_terminals(ListArgs<P> a, typena
               view.sends = ms;
               view.nsends = n;
             }
+            if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
+            view.row_hits = row_hits;
             const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
             if (v >= V_TERM_EXCEPTION) {
               cand = true;
@@ -1924,7 +1942,10 @@ __global__ void __launch_bounds__(kBlock) k_dfs(DfsArgs a, typename P::Params pr
           ended = true;
           break;
         } else {
-          const NodeView view{nxt, P::kNodeWords, -1, nullptr};
+          NodeView view{nxt, P::kNodeWords, -1, nullptr};
+          if constexpr (FIELD) {  // a materialized row: the network leaves scan all of it
+            if (set.n_net) view.row_hits = row_net_hits<P>(set, nxt);
+          }
           v = judge_view<P, FIELD>(view, prm, set, a.init_depth + dep + 1, &pi);
         }
         if (v >= V_TERM_EXCEPTION) {

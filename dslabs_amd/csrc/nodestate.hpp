@@ -141,6 +141,13 @@ struct NodeView {
   // predicates, never an event
   const void* dropped = nullptr;
   int ndropped = 0;
+  // the generic network leaves (DSL_PRED_NET): bit i = a record NEW to the parent's set satisfies
+  // network leaf i (DevPred::pad). The kernels compute it from the delta's registers
+  // (delta_net_hits), host code from `sends` (judge_view); 0 for a materialized row
+  uint32_t net_hits = 0;
+  // bit i = a record of the row at `base`, or a dropped record, satisfies network leaf i
+  // (row_net_hits); filled in only when the judge needs it (net_needs_row)
+  uint32_t row_hits = 0;
   DSL_HD const uint32_t* node(int i) const { return i == changed ? over : base + i * nw; }
 };
 
@@ -606,12 +613,104 @@ DSL_HD bool field_leaf_unchanged(const DevPred& pr, const NodeView& v) {
   return d == 0;
 }
 
-// kField (here and below): the judge knows the field leaf. Host code always does; a kernel is
+// ---- the generic network leaf (DSL_PRED_NET, include/dslabs_hip.h) -------------------------------
+// "network() holds a record satisfying all of the leaf's conditions", each an unsigned comparison
+// of a bit field of the record with a constant; judged here for every protocol.
+// Within one search the network only grows (delivery never removes a record, and the dropped
+// records are constant), so the leaf can differ between a parent and its successor only through
+// the successor's NEW records: when none of them matches, the leaf has the parent's value,
+// whatever that was (also inside a program, where the parent's leaf value is unknown); when one
+// matches it is true without a look at the parent.
+template <class Rec>
+DSL_HD bool rec_cond_holds(const DevRecCond c, Rec r) {
+  uint32_t x;
+  if constexpr (sizeof(Rec) == 8) x = (uint32_t)((uint64_t)r >> c.bit);  // may cross bit 32: shifted as one value
+  else x = (uint32_t)r >> c.bit;
+  if (c.width < 32) x &= (1u << c.width) - 1u;  // no 1u << 32
+  // DSL_CMP_*: bits 1-2 pick ==, < or <=; bit 0 negates (NE, GE, GT)
+  const bool base = (c.cmp >> 1) == 0 ? x == c.k : (c.cmp >> 1) == 1 ? x < c.k : x <= c.k;
+  return base != (bool)(c.cmp & 1u);
+}
+template <class Rec>
+DSL_HD bool rec_matches(const DevRecCond* conds, int n, Rec r) {
+  bool ok = true;
+  for (int i = 0; i < n; i++) ok &= rec_cond_holds<Rec>(conds[i], r);
+  return ok;
+}
+// The hit mask (NodeView::net_hits) of a successor from its delta. Every access to the send list
+// uses a compile-time index (the loop over the sends is innermost and fully unrolled, the
+// conditions are read with wave-uniform indexes), so the records stay in VGPRs: no LDS staging,
+// no scratch. `alive` bit q: kept send q has satisfied the leaf's conditions so far.
+template <class P>
+DSL_HD uint32_t delta_net_hits(const DevSettings& set, const Delta<P>& d) {
+  uint32_t hits = 0;
+  if (d.keep == 0u) return 0u;
+  for (int i = 0; i < set.n_ops; i++) {
+    const DevPred& op = set.ops[i];
+    if (op.id != DSL_PRED_NET) continue;
+    uint32_t alive = d.keep;
+    for (int c = 0; c < op.arg1; c++) {
+      const DevRecCond rc = set.rec_conds[op.arg0 + c];
+#pragma unroll
+      for (int q = 0; q < P::kMaxSends; q++)
+        if (((alive >> q) & 1u) && !rec_cond_holds<typename P::Rec>(rc, d.out.r[q])) alive &= ~(1u << q);
+    }
+    if (alive) hits |= 1u << op.pad;
+  }
+  return hits;
+}
+// The same from a compacted list of the new records (host code).
+template <class P>
+inline uint32_t sends_net_hits(const DevSettings& set, const typename P::Rec* s, int n) {
+  uint32_t hits = 0;
+  for (int i = 0; i < set.n_ops; i++) {
+    const DevPred& op = set.ops[i];
+    if (op.id != DSL_PRED_NET) continue;
+    for (int j = 0; j < n; j++)
+      if (rec_matches<typename P::Rec>(set.rec_conds + op.arg0, op.arg1, s[j])) hits |= 1u << op.pad;
+  }
+  return hits;
+}
+// The same for the records a whole row holds and the dropped records (NodeView::row_hits): the
+// scan of the parent's network(). The kernels run it where few registers are live (before the
+// handler), and only when the judge will ask for it (net_needs_row): never on the common path,
+// where a leaf is a whole predicate and the view is incremental.
+template <class P>
+DSL_HD uint32_t row_net_hits(const DevSettings& set, const uint32_t* w) {
+  using Rec = typename P::Rec;
+  uint32_t hits = 0;
+  const int n = Net<P>::size(w);
+  const Rec* x = static_cast<const Rec*>(set.dropped());
+  for (int i = 0; i < set.n_ops; i++) {
+    const DevPred& op = set.ops[i];
+    if (op.id != DSL_PRED_NET) continue;
+    bool m = false;
+    for (int j = 0; j < n && !m; j++) m = rec_matches<Rec>(set.rec_conds + op.arg0, op.arg1, Net<P>::at(w, j));
+    for (int j = 0; j < set.n_dropped && !m; j++) m = rec_matches<Rec>(set.rec_conds + op.arg0, op.arg1, x[j]);
+    if (m) hits |= 1u << op.pad;
+  }
+  return hits;
+}
+// Whether judging a view needs row_hits: not when every program is one leaf and the view is
+// incremental -- a network leaf is then either skipped (no new record matches: the parent's
+// value) or true by its new records. Inside a program every leaf is evaluated once any leaf
+// changed, a network leaf without a hit too, and a view that is not incremental evaluates all.
+DSL_HD bool net_needs_row(const DevSettings& set, bool incremental, int changed) {
+  return set.n_net != 0 && !(incremental && changed >= 0 && set.flat);
+}
+// A new record matches, or one of the row's, or a dropped one.
+DSL_HD int eval_net_leaf(const DevPred& pr, const NodeView& v) {
+  return (((v.net_hits | v.row_hits) >> pr.pad) & 1u) ? PV_TRUE : PV_FALSE;
+}
+DSL_HD bool net_leaf_unchanged(const DevPred& pr, const NodeView& v) { return !((v.net_hits >> pr.pad) & 1u); }
+
+// kField (here and below): the judge knows the generic leaves (the field leaf and the network leaf). Host code always does; a kernel is
 // instantiated without it for the searches whose settings hold none (kernels.hpp: FIELD).
 template <class P, bool kField = true>
 DSL_HD bool leaf_unchanged(const DevPred& pr, const NodeView& v) {
   if constexpr (kField) {
     if (pr.id == DSL_PRED_FIELD) return field_leaf_unchanged(pr, v);
+    if (pr.id == DSL_PRED_NET) return net_leaf_unchanged(pr, v);
   }
   if (pr.reads >> 31) return false;
   if (!((pr.reads >> v.changed) & 1u)) return true;
@@ -650,7 +749,9 @@ DSL_HD int eval_prog(const DevSettings& set, DevProg g, const NodeView& v, const
       x = a == PV_THREW ? PV_THREW : !a;
     } else {
       if constexpr (kField) {
-        x = op.id == DSL_PRED_FIELD ? eval_field_leaf(op, v) : P::eval(op, v, prm);
+        x = op.id == DSL_PRED_FIELD ? eval_field_leaf(op, v)
+            : op.id == DSL_PRED_NET ? eval_net_leaf(op, v)
+                                    : P::eval(op, v, prm);
       } else {
         x = P::eval(op, v, prm);
       }
@@ -699,6 +800,14 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
     v.dropped = set.dropped();
     v.ndropped = set.n_dropped;
   }
+#ifndef __HIP_DEVICE_COMPILE__
+  // host code hands over the new records as a list and leaves the row's scan to the judge (the
+  // kernels computed both masks themselves: net_hits from registers, row_hits ahead of the handler)
+  if (set.n_net) {
+    if (v.sends) v.net_hits |= sends_net_hits<P>(set, static_cast<const typename P::Rec*>(v.sends), v.nsends);
+    if (net_needs_row(set, incremental, v.changed)) v.row_hits = row_net_hits<P>(set, v.base);
+  }
+#endif
   const int ng = set.n_inv + set.n_goal, nt = ng + set.n_prune;
   if (set.flat) {
     // every program is one leaf (resolve_settings): program t IS ops[t], in checkState order
@@ -710,6 +819,8 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
       if constexpr (kField) {
         x = op.id == DSL_PRED_FIELD
                 ? eval_field_leaf(op, v)
+            : op.id == DSL_PRED_NET
+                ? eval_net_leaf(op, v)
                 : EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
       } else {
         x = EvalHeld<P>::eval(op, v, prm, incremental && v.changed >= 0 && t < set.n_inv && !op.negate);
@@ -762,6 +873,8 @@ void set_pred_reads(DevSettings& d, const typename P::Params& prm) {
     if (op.id == DSL_PRED_FIELD) {
       op.reads = 1u << DSL_FIELD_NODE((uint32_t)op.arg0);
       if (op.pad & kFieldRhsIsField) op.reads |= 1u << DSL_FIELD_NODE((uint32_t)op.arg1);
+    } else if (op.id == DSL_PRED_NET) {
+      op.reads = 1u << 31;  // the network only (its own incremental rule: net_leaf_unchanged)
     } else if (op.id > 0) {
       op.reads = P::pred_reads(op, prm);
     }
@@ -782,6 +895,24 @@ bool check_field_leaves(const DevSettings& d, std::string* why) {
         *why = std::string("field predicate: ") + (k ? "right" : "left") + " operand (node " +
                std::to_string(DSL_FIELD_NODE(descs[k])) + ", bit " + std::to_string(bit) + ", width " +
                std::to_string(width) + "): beyond the node's " + std::to_string(32 * P::kNodeWords) + " bits";
+        return false;
+      }
+    }
+  }
+  return true;
+}
+
+// The same for a network leaf: every condition's field lies inside the record.
+template <class P>
+bool check_net_leaves(const DevSettings& d, std::string* why) {
+  for (int i = 0; i < d.n_ops; i++) {
+    const DevPred& op = d.ops[i];
+    if (op.id != DSL_PRED_NET) continue;
+    for (int c = 0; c < op.arg1; c++) {
+      const DevRecCond& rc = d.rec_conds[op.arg0 + c];
+      if (rc.bit + rc.width > 8 * (int)sizeof(typename P::Rec)) {
+        *why = "network predicate: condition " + std::to_string(c) + " (bit " + std::to_string(rc.bit) + ", width " +
+               std::to_string(rc.width) + "): beyond the record's " + std::to_string(8 * sizeof(typename P::Rec)) + " bits";
         return false;
       }
     }

@@ -75,7 +75,8 @@ struct TraceTool {
   }
 
   int eval(DevProg g, const State& s) const {
-    const NodeView v{s.w, P::kNodeWords, -1, nullptr};
+    NodeView v{s.w, P::kNodeWords, -1, nullptr};
+    if (search.n_net) v.row_hits = row_net_hits<P>(search, s.w);  // what judge_view prepares for the network leaves
     return eval_prog<P>(search, g, v, prm);
   }
 

@@ -48,6 +48,7 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
   d.n_prune = in.n_prunes;
   // predicate trees (leaves + DSL_PRED_AND / _OR / _IMPLIES over pool entries) -> postfix programs
   std::string why;
+  int n_rec = 0;  // entries of d.rec_conds in use
   std::function<bool(const dsl_predicate&, int, int*)> emit = [&](const dsl_predicate& p, int level, int* sp) -> bool {
     if (level > 16) return why = "predicate nesting too deep", false;
     const bool comb = p.pred_id == DSL_PRED_AND || p.pred_id == DSL_PRED_OR || p.pred_id == DSL_PRED_IMPLIES;
@@ -94,6 +95,39 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
       if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
       return true;
     }
+    if (p.pred_id == DSL_PRED_NET) {
+      // the generic network leaf: every protocol's. Its conditions (consecutive DSL_PRED_REC_COND
+      // pool entries) go into DevSettings::rec_conds; the DevPred keeps (first, count) and the
+      // leaf's ordinal. bit + width against the record's size is check_net_leaves<P>'s.
+      if (p.arg1 < 1 || p.arg1 > DSL_MAX_NET_CONDS)
+        return why = "network predicate: " + std::to_string(p.arg1) + " conditions, outside 1.." +
+                     std::to_string(DSL_MAX_NET_CONDS), false;
+      if (p.arg0 < 0 || p.arg0 > in.n_pool || p.arg0 + p.arg1 > in.n_pool)
+        return why = "network predicate: condition range outside dsl_settings.pool", false;
+      if (n_rec + (int)p.arg1 > kMaxRecConds)
+        return why = "network predicate: more than " + std::to_string(kMaxRecConds) + " conditions in all", false;
+      const int first = n_rec;
+      for (int c = 0; c < (int)p.arg1; c++) {
+        const dsl_predicate& q = in.pool[p.arg0 + c];
+        const std::string at = "network predicate: condition " + std::to_string(c) + " (pool " + std::to_string(p.arg0 + c) + "): ";
+        if (q.pred_id != DSL_PRED_REC_COND) return why = at + "not a DSL_PRED_REC_COND", false;
+        const uint64_t a0 = (uint64_t)q.arg0, a1 = (uint64_t)q.arg1;
+        const int width = DSL_REC_ARG0_WIDTH(a0), cmp = DSL_REC_ARG0_CMP(a0);
+        if (q.negate) return why = at + "negate set on a record condition", false;
+        if (a0 & ~DSL_REC_ARG0_MASK) return why = at + "arg0 has bits set outside bit, width and comparison", false;
+        if (cmp > DSL_CMP_GT) return why = at + "unknown comparison " + std::to_string(cmp), false;
+        if (width < 1 || width > 32) return why = at + "width outside 1..32", false;
+        if (a1 >> 32) return why = at + "arg1 does not fit in 32 unsigned bits", false;
+        d.rec_conds[n_rec++] = DevRecCond{(uint16_t)DSL_REC_ARG0_BIT(a0), (uint8_t)width, (uint8_t)cmp, (uint32_t)a1};
+      }
+      if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
+      d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, first, (int32_t)p.arg1, 0u, (uint32_t)d.n_net++};
+      if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
+      return true;
+    }
+    if (p.pred_id == DSL_PRED_REC_COND)
+      return why = "record condition (DSL_PRED_REC_COND) used as a predicate or a combinator operand: "
+                   "it is legal only as a condition of a DSL_PRED_NET", false;
     if (!known(p.pred_id)) return why = "predicate not supported by this protocol's device predicates", false;
     if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
     d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, (int32_t)p.arg0, (int32_t)p.arg1, 0u, 0u};

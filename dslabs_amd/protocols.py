@@ -64,6 +64,16 @@ class Protocol:
             isinstance(address, int) and 0 <= address < len(self.addresses) else repr(address)
         return make_field_ref(self, address, bit, width, f"{name}.bits[{bit}:{bit + width}]")
 
+    def raw_message(self, label: str = "message", rec_bits: int = 64):
+        """A pattern over any record of the packed network, for a caller who knows the record
+        layout (csrc/protocols/*.hpp): ``m = proto.raw_message(); m.where(m.raw_field(0, 8) >= 2)``
+        is "a record whose bits 0..7 are >= 2 is in the network": a StatePredicate judged on the
+        device. ``rec_bits``: the record's size, 32 or 64 (the engine checks it again)."""
+        from .search import MessagePattern
+        if rec_bits not in (32, 64):
+            raise ValueError("rec_bits is 32 or 64")
+        return MessagePattern(self, label, (), None, rec_bits)
+
 
 class PingPong(Protocol):
     """lab0 PingPong: 1 server ("pingserver"), ``clients`` ClientWorkers with
@@ -729,6 +739,27 @@ class IRProtocol(Protocol):
         if not f.cap or f.array:
             raise ValueError(f"{label} is not a bounded list: it has no length")
         return make_field_ref(self, address, f.len_off, f.len_bits, f"length({label})")
+
+    def message(self, name: str, frm=None, to=None):
+        """Messages of type ``name``, from ``frm`` and to ``to`` when given, as a MessagePattern:
+        ``vr = pb.message("ViewReply"); vr.where(vr.field("viewNum") >= 4)`` is hasViewReply(4)."""
+        from .search import CMP_EQ, MessagePattern, RecCond
+        sp = self.spec
+        sp.layout()
+        m = next((x for x in sp.messages if x.name == name), None)
+        if m is None:
+            raise ValueError(f"unknown message {name!r}: the protocol's are {[x.name for x in sp.messages]}")
+        base = [RecCond(sp.type_off, sp.type_bits, CMP_EQ, m.index, f"type == {name}")]
+        label = name
+        for what, adr, off in (("from", frm, sp.from_off), ("to", to, sp.to_off)):
+            if adr is None:
+                continue
+            node = self.address_index(adr)
+            if isinstance(node, bool) or not 0 <= node < len(self.addresses):
+                raise ValueError(f"unknown address {adr!r}")
+            base.append(RecCond(off, sp.addr_bits, CMP_EQ, node, f"{what} == {self.addresses[node]}"))
+            label += f" {what} {self.addresses[node]}"
+        return MessagePattern(self, label, base, {n: (off, b) for n, b, off in m.offs}, sp.rec_bits)
 
     def render_event(self, e) -> str:
         a = self.addresses

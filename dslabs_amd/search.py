@@ -71,6 +71,23 @@ def field_arg0_decode(arg0: int) -> tuple:
     return arg0 & 0xFFFFFFFF, (arg0 >> 32) & 7, bool((arg0 >> 35) & 1)
 
 
+# the generic network leaf (DSL_PRED_NET) and its conditions (DSL_PRED_REC_COND)
+PRED_NET = 951
+PRED_REC_COND = 952
+MAX_NET_CONDS = 8         # DSL_MAX_NET_CONDS: conditions of one leaf
+MAX_NET_CONDS_TOTAL = 32  # DSL_MAX_NET_CONDS_TOTAL: conditions of all the leaves of one search
+
+
+def rec_arg0(bit: int, width: int, cmp: int) -> int:
+    """DSL_REC_ARG0: bit (bits 0-15) | width << 16 (bits 16-21) | comparison << 32 (bits 32-34)."""
+    return bit | (width << 16) | (cmp << 32)
+
+
+def rec_arg0_decode(arg0: int) -> tuple:
+    """(bit, width, comparison) of a record condition's arg0 (DSL_REC_ARG0_BIT / _WIDTH / _CMP)."""
+    return arg0 & 0xFFFF, (arg0 >> 16) & 0x3F, (arg0 >> 32) & 7
+
+
 class StatePredicate:
     """A named state predicate evaluated on the device (StatePredicate.java).
 
@@ -81,8 +98,10 @@ class StatePredicate:
     """
 
     def __init__(self, name: str, pred_id: int, arg0=0, arg1=0, negated: bool = False,
-                 address_args: Sequence[int] = (), operands: Sequence["StatePredicate"] = ()):
+                 address_args: Sequence[int] = (), operands: Sequence["StatePredicate"] = (),
+                 conds: Sequence["RecCond"] = ()):
         self.name = name
+        self.conds = tuple(conds)  # PRED_NET: the record conditions (pool entries when encoded)
         self.pred_id = pred_id
         self.arg0 = arg0
         self.arg1 = arg1
@@ -97,7 +116,7 @@ class StatePredicate:
         else:
             name = f"¬({self.name})"
         return StatePredicate(name, self.pred_id, self.arg0, self.arg1, not self.negated, self.address_args,
-                              self.operands)
+                              self.operands, self.conds)
 
     def and_(self, other: "StatePredicate") -> "StatePredicate":
         return StatePredicate(f"({self.name}) ∧ ({other.name})", PRED_AND, operands=(self, other))
@@ -109,7 +128,13 @@ class StatePredicate:
         return StatePredicate(f"({self.name}) → ({other.name})", PRED_IMPLIES, operands=(self, other))
 
     def _encode(self, state: "SearchState", pool: list) -> _lib.dsl_predicate:
-        """The C ABI form; a combinator's operands are appended to ``pool`` (dsl_settings.pool)."""
+        """The C ABI form; a combinator's operands and a network leaf's conditions are appended to
+        ``pool`` (dsl_settings.pool)."""
+        if self.pred_id == PRED_NET:
+            first = len(pool)
+            for c in self.conds:  # consecutive pool entries
+                pool.append(_lib.dsl_predicate(PRED_REC_COND, 0, rec_arg0(c.bit, c.width, c.cmp), c.const))
+            return _lib.dsl_predicate(PRED_NET, 1 if self.negated else 0, first, len(self.conds))
         if self.operands:
             idx = []
             for op in self.operands:
@@ -214,10 +239,130 @@ def make_field_ref(protocol, address, bit: int, width: int, name: str) -> FieldR
     return FieldRef(protocol, node, bit, width, name)
 
 
+class RecCond:
+    """One condition of a message pattern: ``width`` bits from bit ``bit`` of the packed record
+    compared (unsigned, DSL_CMP_*) with a constant."""
+
+    def __init__(self, bit: int, width: int, cmp: int, const: int, text: str):
+        self.bit, self.width, self.cmp, self.const, self.text = bit, width, cmp, const, text
+
+    def holds(self, rec: int) -> bool:
+        x = (rec >> self.bit) & ((1 << self.width) - 1)
+        return {CMP_EQ: x == self.const, CMP_NE: x != self.const, CMP_LT: x < self.const, CMP_GE: x >= self.const,
+                CMP_LE: x <= self.const, CMP_GT: x > self.const}[self.cmp]
+
+    def __repr__(self) -> str:
+        return self.text
+
+
+class RecFieldRef:
+    """A bit field of a message's packed record (``MessagePattern.field`` / ``raw_field``):
+    comparing it with an int gives a RecCond for ``MessagePattern.where``."""
+
+    def __init__(self, bit: int, width: int, name: str):
+        self.bit, self.width, self.name = bit, width, name
+
+    def _cmp(self, cmp: int, other) -> RecCond:
+        if isinstance(other, bool) or not isinstance(other, int):
+            raise TypeError(f"{self.name}: compare with an int, not {type(other).__name__}")
+        if other < 0 or other >= 1 << self.width:
+            raise ValueError(f"{self.name}: constant {other} does not fit in the field's {self.width} bits")
+        return RecCond(self.bit, self.width, cmp, other, f"{self.name} {_CMP_TEXT[cmp]} {other}")
+
+    def eq(self, other) -> RecCond:
+        return self._cmp(CMP_EQ, other)
+
+    def ne(self, other) -> RecCond:
+        return self._cmp(CMP_NE, other)
+
+    def lt(self, other) -> RecCond:
+        return self._cmp(CMP_LT, other)
+
+    def le(self, other) -> RecCond:
+        return self._cmp(CMP_LE, other)
+
+    def gt(self, other) -> RecCond:
+        return self._cmp(CMP_GT, other)
+
+    def ge(self, other) -> RecCond:
+        return self._cmp(CMP_GE, other)
+
+    __eq__, __ne__, __lt__, __le__, __gt__, __ge__ = eq, ne, lt, le, gt, ge
+    __hash__ = object.__hash__
+
+    def __repr__(self) -> str:
+        return self.name
+
+
+def _check_rec_field(name: str, bit: int, width: int, rec_bits: int) -> None:
+    if isinstance(bit, bool) or isinstance(width, bool) or not isinstance(bit, int) or not isinstance(width, int):
+        raise TypeError(f"{name}: bit and width are ints")
+    if not 1 <= width <= 32:
+        raise ValueError(f"{name}: width {width} outside 1..32")
+    if bit < 0 or bit + width > rec_bits:
+        raise ValueError(f"{name}: bits {bit}..{bit + width - 1} outside the record's {rec_bits} bits")
+
+
+class MessagePattern:
+    """Messages of one type, optionally from / to given addresses (``IRProtocol.message``), or any
+    record of a hand-written protocol (``Protocol.raw_message``). ``where(cond, ...)`` gives the
+    StatePredicate "the network (dropped messages included) holds a message of this pattern that
+    satisfies every condition": StatePredicate.containsMessageMatching (StatePredicate.java:139-149)
+    for a conjunction of field comparisons, judged on the device (DSL_PRED_NET)."""
+
+    def __init__(self, protocol, label: str, base: Sequence[RecCond], fields, rec_bits: int):
+        self.protocol, self.label, self.base, self.fields, self.rec_bits = protocol, label, tuple(base), fields, rec_bits
+
+    def field(self, name: str) -> RecFieldRef:
+        """Field ``name`` of the message type (fields pack from bit 0 in declaration order)."""
+        if self.fields is None:
+            raise ValueError(f"{self.label}: a raw message has no named fields (use raw_field)")
+        if name not in self.fields:
+            raise ValueError(f"{self.label} has no field {name!r}")
+        bit, width = self.fields[name]
+        _check_rec_field(f"{self.label}.{name}", bit, width, self.rec_bits)
+        return RecFieldRef(bit, width, name)
+
+    def raw_field(self, bit: int, width: int) -> RecFieldRef:
+        """``width`` bits (1..32) from bit ``bit`` of the packed record, for a caller who knows
+        the layout (csrc/protocols/*.hpp)."""
+        _check_rec_field(f"{self.label}.bits[{bit}:{bit + width}]", bit, width, self.rec_bits)
+        return RecFieldRef(bit, width, f"bits[{bit}:{bit + width}]")
+
+    def where(self, *conds: RecCond) -> StatePredicate:
+        for c in conds:
+            if not isinstance(c, RecCond):
+                raise TypeError(f"{self.label}.where: a condition is a comparison of a field of the message "
+                                f"with an int, not {type(c).__name__}")
+            if c.bit + c.width > self.rec_bits:
+                raise ValueError(f"{self.label}.where: {c.text} lies outside the record's {self.rec_bits} bits")
+        allc = self.base + tuple(conds)
+        if not allc:
+            raise ValueError(f"{self.label}.where: no condition at all")
+        if len(allc) > MAX_NET_CONDS:
+            raise ValueError(f"{self.label}.where: {len(allc)} conditions, at most {MAX_NET_CONDS} "
+                             "(message type and addresses included)")
+        name = f"contains {self.label}" + (f"({', '.join(c.text for c in conds)})" if conds else "")
+        return StatePredicate(name, PRED_NET, conds=allc)
+
+    def __repr__(self) -> str:
+        return self.label
+
+
+def message_matches(state: "SearchState", pred: StatePredicate) -> List[int]:
+    """The records of ``state``'s network(), dropped ones included, that satisfy every condition of
+    the message predicate ``pred`` (negation ignored), decoded on the host: empty when the
+    device's leaf is false."""
+    if pred.pred_id != PRED_NET:
+        raise ValueError(f"{pred.name!r} is not a message predicate")
+    return [r for r in state.records() if all(c.holds(r) for c in pred.conds)]
+
+
 def statePredicate(name: str, pred: StatePredicate) -> StatePredicate:
     """StatePredicate.statePredicate(name, fn) (StatePredicate.java:168-176) for a predicate built
     from field comparisons and combinators: the same predicate under ``name``."""
-    return StatePredicate(name, pred.pred_id, pred.arg0, pred.arg1, pred.negated, pred.address_args, pred.operands)
+    return StatePredicate(name, pred.pred_id, pred.arg0, pred.arg1, pred.negated, pred.address_args, pred.operands,
+                          pred.conds)
 
 
 def _fold(preds, op: str, what: str) -> StatePredicate:
@@ -465,7 +610,10 @@ class SearchSettings:
             for i, p in enumerate(lst):
                 arr[i] = p._encode(state, pool)
         if len(pool) > _lib.DSL_MAX_POOL:
-            raise ValueError("too many combinator operands")
+            raise ValueError(f"too many combinator operands and message conditions: {len(pool)} pool entries, "
+                             f"at most {_lib.DSL_MAX_POOL}")
+        if sum(p.pred_id == PRED_REC_COND for p in pool) > MAX_NET_CONDS_TOTAL:
+            raise ValueError(f"too many message conditions in one search: at most {MAX_NET_CONDS_TOTAL}")
         s.n_pool = len(pool)
         for i, p in enumerate(pool):
             s.pool[i] = p
@@ -548,6 +696,13 @@ class SearchState:
     def droppedMessages(self) -> List[int]:
         """The dropped set as packed records (sorted)."""
         return list(self._dropped)
+
+    def records(self) -> List[int]:
+        """network() as packed records (sorted): the state's own and the dropped ones
+        (SearchState.java:153-157), what a message predicate reads."""
+        c = SearchState(self.protocol, self._packed_now(), dropped=self._dropped)
+        c.dropPendingMessages()
+        return c.droppedMessages()
 
     def depth(self) -> int:
         return self._depth

@@ -41,8 +41,9 @@ extern "C" {
                             5: dsl_stats deduped;
                             6: dsl_settings.max_terminals, dsl_result terminals_total / n_terminals /
                                terminals, dsl_terminal.
-                            Still 6 with DSL_PRED_FIELD: a new dsl_predicate_id changes no struct and adds
-                            no entry point; a library without it answers DSL_ERR_UNKNOWN_PREDICATE */
+                            Still 6 with DSL_PRED_FIELD and DSL_PRED_NET / _REC_COND: a new dsl_predicate_id
+                            changes no struct and adds no entry point; a library without it answers
+                            DSL_ERR_UNKNOWN_PREDICATE */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -134,7 +135,20 @@ typedef enum {
    * words with a constant or with a second bit field. Every protocol accepts it; it never throws;
    * negate applies as for any leaf and it may be an operand of the combinators. Encoding below
    * (DSL_FIELD_*). A bad descriptor is refused by dsl_set_settings with DSL_ERR_ARG. */
-  DSL_PRED_FIELD = 950
+  DSL_PRED_FIELD = 950,
+  /* The generic network leaf (StatePredicate.containsMessageMatching(name, fn),
+   * T/StatePredicate.java:139-149, for fn = a conjunction of comparisons of record fields with
+   * constants): true when network() -- the state's records and the dropped records,
+   * SearchState.java:153-157 -- holds a record that satisfies ALL of the leaf's conditions.
+   * arg0 = index of the first condition in dsl_settings.pool, arg1 = number of conditions
+   * (1 .. DSL_MAX_NET_CONDS); the conditions are consecutive DSL_PRED_REC_COND pool entries. Every
+   * protocol accepts it; it never throws; negate applies as for any leaf and it may be an operand
+   * of the combinators. A bad leaf is refused by dsl_set_settings with DSL_ERR_ARG. */
+  DSL_PRED_NET = 951,
+  /* One condition of a DSL_PRED_NET: an unsigned comparison of a bit field of the record with a
+   * constant. Legal only as a pool entry that a DSL_PRED_NET refers to (never a predicate, never a
+   * combinator's operand); negate must be 0. Encoding below (DSL_REC_*). */
+  DSL_PRED_REC_COND = 952
 } dsl_predicate_id;
 
 /* DSL_PRED_FIELD. A field descriptor (27 bits) names `width` bits (1..32) from bit `bit` of node
@@ -163,6 +177,22 @@ typedef enum {
 #define DSL_FIELD_ARG0_DESC(arg0) ((uint32_t)((uint64_t)(arg0) & 0xffffffffu))
 #define DSL_FIELD_ARG0_CMP(arg0) ((int)(((uint64_t)(arg0) >> 32) & 7u))
 #define DSL_FIELD_ARG0_RHS_IS_FIELD(arg0) ((int)(((uint64_t)(arg0) >> 35) & 1u))
+
+/* DSL_PRED_REC_COND. `width` bits (1..32) from bit `bit` of the protocol's packed record (bit 0 =
+ * the record's least significant bit; bit + width <= 8 * the record's size in bytes; on a 64-bit
+ * record the field may cross bit 32, the record is shifted as one value):
+ *     dsl_predicate.arg0 = bit (bits 0-15) | width << 16 (bits 16-21) | comparison << 32 (bits 32-34);
+ *                          every other bit 0
+ *     dsl_predicate.arg1 = an unsigned constant 0 .. 2^32-1
+ * The condition is  field <comparison> constant  (DSL_CMP_*) over the unsigned field value. */
+#define DSL_MAX_NET_CONDS 8       /* conditions of one DSL_PRED_NET */
+#define DSL_MAX_NET_CONDS_TOTAL 32 /* conditions of all the network leaves of one dsl_settings */
+#define DSL_REC_ARG0(bit, width, cmp) \
+  ((int64_t)(uint32_t)(bit) | ((int64_t)(uint32_t)(width) << 16) | ((int64_t)(cmp) << 32))
+#define DSL_REC_ARG0_BIT(arg0) ((int)((uint64_t)(arg0) & 0xffffu))
+#define DSL_REC_ARG0_WIDTH(arg0) ((int)(((uint64_t)(arg0) >> 16) & 0x3fu))
+#define DSL_REC_ARG0_CMP(arg0) ((int)(((uint64_t)(arg0) >> 32) & 7u))
+#define DSL_REC_ARG0_MASK 0x00000007003fffffull
 
 typedef struct {
   int32_t pred_id;   /* dsl_predicate_id */

@@ -24,8 +24,15 @@ import java.util.function.Function;
 public final class GpuPredicates {
   static final int AND = 900, OR = 901, IMPLIES = 902;
 
-  /** A predicate leaf on the device: id and two integer arguments. */
-  public record Leaf(int id, long arg0, long arg1) {}
+  /**
+   * A predicate leaf on the device: id and two integer arguments. A network leaf (NET) also has its
+   * record conditions, which the encoder writes to the pool (arg0 / arg1 become their range).
+   */
+  public record Leaf(int id, long arg0, long arg1, List<Leaf> conds) {
+    public Leaf(int id, long arg0, long arg1) {
+      this(id, arg0, arg1, List.of());
+    }
+  }
 
   /** DSL_PRED_FIELD and its comparisons (DSL_CMP_*): a leaf every protocol accepts. */
   public static final int FIELD = 950;
@@ -46,7 +53,26 @@ public final class GpuPredicates {
     return new Leaf(FIELD, desc | ((long) cmp << 32) | (1L << 35), otherDesc);
   }
 
-  private record Tree(int id, boolean negate, long arg0, long arg1, Tree left, Tree right) {}
+  /** DSL_PRED_NET and DSL_PRED_REC_COND: "network() holds a record satisfying every condition". */
+  public static final int NET = 951, REC_COND = 952, MAX_NET_CONDS = 8;
+
+  /** DSL_REC_ARG0: width bits (1..32) from bit `bit` of the packed record, compared with a constant. */
+  public static Leaf recCond(int bit, int width, int cmp, long constant) {
+    return new Leaf(REC_COND, (long) bit | ((long) width << 16) | ((long) cmp << 32), constant);
+  }
+
+  /** The network leaf over 1..MAX_NET_CONDS conditions (recCond); null when there are none or too many. */
+  public static Leaf net(List<Leaf> conds) {
+    if (conds.isEmpty() || conds.size() > MAX_NET_CONDS) return null;
+    for (Leaf c : conds) if (c.id() != REC_COND) return null;
+    return new Leaf(NET, 0, conds.size(), List.copyOf(conds));
+  }
+
+  private record Tree(int id, boolean negate, long arg0, long arg1, Tree left, Tree right, List<Leaf> conds) {
+    Tree(int id, boolean negate, long arg0, long arg1, Tree left, Tree right) {
+      this(id, negate, arg0, arg1, left, right, List.of());
+    }
+  }
 
   private GpuPredicates() {}
 
@@ -113,6 +139,16 @@ public final class GpuPredicates {
       pool.add(t.right());
       if (!write(m, Dsl.OFF_POOL + Dsl.SIZE_PREDICATE * a1, t.right(), pool)) return false;
     }
+    if (t.id() == NET) {  // the conditions: consecutive pool entries, the leaf keeps (first, count)
+      a0 = pool.size();
+      a1 = t.conds().size();
+      for (Leaf c : t.conds()) {
+        Tree ct = new Tree(c.id(), false, c.arg0(), c.arg1(), null, null);
+        long at = pool.size();
+        pool.add(ct);
+        if (!write(m, Dsl.OFF_POOL + Dsl.SIZE_PREDICATE * at, ct, pool)) return false;
+      }
+    }
     if (pool.size() > Dsl.MAX_POOL) return false;
     m.set(ValueLayout.JAVA_INT, off + Dsl.OFF_PRED_ID, t.id());
     m.set(ValueLayout.JAVA_INT, off + Dsl.OFF_PRED_NEGATE, t.negate() ? 1 : 0);
@@ -124,10 +160,10 @@ public final class GpuPredicates {
   // The combinator structure back from StatePredicate's names.
   static Tree parse(String name, Function<String, Leaf> leaf) {
     Leaf l = leaf.apply(name);
-    if (l != null) return new Tree(l.id(), false, l.arg0(), l.arg1(), null, null);
+    if (l != null) return new Tree(l.id(), false, l.arg0(), l.arg1(), null, null, l.conds());
     if (name.startsWith("¬(") && name.endsWith(")")) {
       Tree t = parse(name.substring(2, name.length() - 1), leaf);
-      return t == null ? null : new Tree(t.id(), !t.negate(), t.arg0(), t.arg1(), t.left(), t.right());
+      return t == null ? null : new Tree(t.id(), !t.negate(), t.arg0(), t.arg1(), t.left(), t.right(), t.conds());
     }
     if (!name.startsWith("(")) return null;
     int depth = 0;

@@ -67,7 +67,7 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
   std::string why;
   if (resolve_settings(hs, P::num_nodes(prm), &P::known_predicate, &set, &why))
     return fprintf(stderr, "settings: %s\n", why.c_str()), 2;
-  if (!check_field_leaves<P>(set, &why)) return fprintf(stderr, "settings: %s\n", why.c_str()), 2;
+  if (!check_field_leaves<P>(set, &why) || !check_net_leaves<P>(set, &why)) return fprintf(stderr, "settings: %s\n", why.c_str()), 2;
   set_pred_reads<P>(set, prm);
   constexpr int NW = Layout<P>::kWords;
   struct Row {

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(HERE, "libdslabs_hip%s.so" % ("_" + _VARIANT if _VARIANT
 DSL_MAX_NODES = 32
 DSL_MAX_PREDICATES = 16
 DSL_MAX_POOL = 48
+DSL_MAX_WATCHES = 8
 DSL_MAX_PARAMS = 64
 DSL_MAX_EVENT_FIELDS = 8
 DSL_PROTO_PINGPONG_IR = 8  # protocols generated from the IR (dslabs_amd/ir/specs)
@@ -39,6 +40,7 @@ EXPORTED = [
     "dsl_set_settings", "dsl_set_initial", "dsl_get_initial", "dsl_run", "dsl_progress",
     "dsl_kernel_stats", "dsl_result_free", "dsl_destroy", "dsl_last_error", "dsl_create_with_host_comm",
     "dsl_run_dfs", "dsl_replay", "dsl_human_readable_trace", "dsl_set_dropped",
+    "dsl_set_watches", "dsl_watch_counts",
 ]
 DSL_ABI_VERSION = 6  # include/dslabs_hip.h; load() refuses a library of another layout
 
@@ -164,6 +166,9 @@ def load() -> ctypes.CDLL:
     lib.dsl_set_initial.argtypes = [ctypes.c_void_p, P(ctypes.c_uint8), ctypes.c_size_t, ctypes.c_int32]
     lib.dsl_get_initial.argtypes = [ctypes.c_void_p, P(ctypes.c_uint8), ctypes.c_size_t]
     lib.dsl_set_dropped.argtypes = [ctypes.c_void_p, P(ctypes.c_uint64), ctypes.c_int32]
+    lib.dsl_set_watches.argtypes = [ctypes.c_void_p, P(dsl_predicate), ctypes.c_int32, P(dsl_predicate), ctypes.c_int32]
+    lib.dsl_watch_counts.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_uint64), ctypes.c_int32,
+                                     P(ctypes.c_int32), P(ctypes.c_uint64)]
     lib.dsl_run.argtypes = [ctypes.c_void_p, P(P(dsl_result))]
     lib.dsl_run_dfs.argtypes = [ctypes.c_void_p, P(dsl_dfs_config), P(P(dsl_result))]
     lib.dsl_replay.argtypes = [ctypes.c_void_p, P(dsl_event), ctypes.c_int32, ctypes.c_int32, P(P(dsl_result))]

@@ -31,7 +31,8 @@
 namespace dsl {
 
 void set_error(const std::string& msg);
-int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out);
+int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out,
+                     const WatchList* watches = nullptr);
 
 #define DSL_HIP(call)                                                                           \
   do {                                                                                          \
@@ -83,6 +84,14 @@ struct EngineBase {
   virtual int set_initial(const uint8_t* p, size_t len, int depth) = 0;
   virtual int get_initial(uint8_t* p, size_t len) = 0;
   virtual int set_dropped(const uint64_t* recs, int n) = 0;
+  virtual int set_watches(const dsl_predicate* w, int n, const dsl_predicate* pool, int n_pool) = 0;
+  // the census of the last run(): per watch, the count per completed level and the total
+  std::vector<std::vector<uint64_t>> watch_census;
+  std::vector<uint64_t> watch_total;
+  void clear_census() {
+    watch_census.clear();
+    watch_total.clear();
+  }
   virtual int run(dsl_result** out) = 0;
   virtual int run_dfs(const dsl_dfs_config& c, dsl_result** out) = 0;
   virtual int replay(const dsl_event* trace, int n, int minimize, dsl_result** out) = 0;
@@ -341,19 +350,43 @@ struct BfsEngine : EngineBase {
   }
 
   int state_bytes() const override { return (int)sizeof(typename P::State); }
-  int set_settings(const dsl_settings& s) override {
+  int set_settings(const dsl_settings& s) override { return resolve_all(s, hwatch, hwpool); }
+  // The watches (dsl_set_watches), kept across set_settings like the dropped set: the settings and
+  // the watches are compiled together (one ops[], one rec_conds[]), so whichever call comes second
+  // and makes a sum overflow is the one refused, and the engine keeps what it had.
+  std::vector<dsl_predicate> hwatch, hwpool;
+  int set_watches(const dsl_predicate* w, int n, const dsl_predicate* pool, int n_pool) override {
+    if (n < 0 || n > DSL_MAX_WATCHES) {
+      set_error("watches: " + std::to_string(n) + ", outside 0.." + std::to_string(DSL_MAX_WATCHES));
+      return DSL_ERR_ARG;
+    }
+    if ((n > 0 && !w) || n_pool < 0 || n_pool > DSL_MAX_POOL || (n_pool > 0 && !pool)) {
+      set_error("watches: predicate counts out of range");
+      return DSL_ERR_ARG;
+    }
+    const std::vector<dsl_predicate> nw(w, w + n), np(pool, pool + (n ? n_pool : 0));
+    const int rc = resolve_all(hset, nw, np);
+    if (rc == DSL_OK) clear_census();
+    return rc;
+  }
+  int resolve_all(const dsl_settings& s, const std::vector<dsl_predicate>& w, const std::vector<dsl_predicate>& wp) {
     DevSettings ds;
-    int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &ds);
+    const WatchList wl{w.data(), (int32_t)w.size(), wp.data(), (int32_t)wp.size()};
+    int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &ds, &wl);
     if (rc == DSL_OK) {
       std::string why;
       if (!check_field_leaves<P>(ds, &why) || !check_net_leaves<P>(ds, &why)) {  // the checks that need P
         set_error(why);
-        return DSL_ERR_ARG;  // the engine keeps the settings it had
+        return DSL_ERR_ARG;  // the engine keeps the settings and the watches it had
       }
       dset = ds;
       hset = s;
+      hwatch = w;
+      hwpool = wp;
       set_pred_reads<P>(dset, prm);
-      field_leaves = false;
+      // a search with watches launches the FIELD instantiation even when every watch is a named
+      // leaf: the watch code lives in k_level<P, false, true> alone (no further instantiation)
+      field_leaves = dset.n_watch > 0;
       for (int i = 0; i < dset.n_ops; i++) field_leaves |= dset.ops[i].id == DSL_PRED_FIELD || dset.ops[i].id == DSL_PRED_NET;
     }
     apply_dropped();
@@ -1609,6 +1642,15 @@ struct BfsEngine : EngineBase {
                 std::to_string(W) + "): run it in one process (virtual shards are supported)");
       return DSL_ERR_ARG;
     }
+    // the watches' census is single-shard: a sharded maxDepth level judges its routed successors
+    // at the source (LevelArgs::judge_routed), which sees a state once per generating shard, so
+    // counting there needs the owner's answer. Refused the same way, before any collective.
+    clear_census();
+    if (dset.n_watch > 0 && W > 1) {
+      set_error("watches are not supported in a search over more than one shard (" + std::to_string(W) +
+                " shards): run it with virtual_shards = 1 and world_size = 1, or clear the watches (dsl_set_watches)");
+      return DSL_ERR_ARG;
+    }
     restart_buckets = 0;
     t_run0 = std::chrono::steady_clock::now();
     for (int attempt = 0;; attempt++) {
@@ -1756,6 +1798,16 @@ struct BfsEngine : EngineBase {
       const NodeView v0{init.w, P::kNodeWords, -1, nullptr};
       const int v = judge_view<P>(v0, prm, dset, init_depth, &pi);
       init_enc = ((uint64_t)v << 32) | (uint32_t)(pi + 1);
+    }
+    // the watches' census of this attempt (a restarted search counts from zero): index i lines up
+    // with per_depth[i]; the start state's watches are evaluated here, with its verdict
+    const int n_watch = dset.n_watch;
+    std::vector<std::vector<uint64_t>> census(n_watch, std::vector<uint64_t>(1, 0));
+    std::vector<uint64_t> census_total(n_watch, 0);
+    if (n_watch) {
+      const NodeView v0{init.w, P::kNodeWords, -1, nullptr};
+      const uint32_t held = eval_watches<P>(v0, prm, dset);
+      for (int w = 0; w < n_watch; w++) census[w][0] = census_total[w] = (held >> w) & 1u;
     }
     for (auto& S : sh) {
       // one k_setup per shard: zeroes its table and counters; seeds the initial state's owner (or
@@ -2223,6 +2275,7 @@ struct BfsEngine : EngineBase {
           // not a completed depth; a terminal it found is still reported (below)
           successors += gsum[2];
           total_states += gsum[0];
+          for (int w = 0; w < n_watch; w++) census_total[w] += sh[0].lc.watch[w];  // as `states`: not a completed level
           progress_states = total_states;
           end = DSL_TIME_EXHAUSTED;
           break;
@@ -2230,6 +2283,10 @@ struct BfsEngine : EngineBase {
         depth++;
         successors += gsum[2];
         total_states += gsum[0];
+        for (int w = 0; w < n_watch; w++) {  // a completed level (single levels and queued ones alike)
+          census_total[w] += sh[0].lc.watch[w];
+          if (gsum[0]) census[w].push_back(sh[0].lc.watch[w]);
+        }
         inserted += route ? max_new : gsum[0];  // per shard (an upper bound)
         prev_new = gsum[0];
         prev_work = gsum[6];
@@ -2438,12 +2495,15 @@ struct BfsEngine : EngineBase {
       fprintf(stderr, "[run] %.4f ms\n",
               std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
     *out = r;
+    watch_census = std::move(census);
+    watch_total = std::move(census_total);
     return DSL_OK;
   }
 
   // Search.dfs on the device (k_dfs): see dsl_run_dfs in include/dslabs_hip.h.
   int run_dfs(const dsl_dfs_config& c, dsl_result** out) override {
     auto t_start = std::chrono::steady_clock::now();
+    clear_census();
     (void)hipGetLastError();
     if (W != 1) {
       set_error("random DFS runs on a single shard");
@@ -2597,6 +2657,7 @@ struct BfsEngine : EngineBase {
 
   // dsl_human_readable_trace: SearchState.humanReadableTrace on the host (replay.hpp).
   int human_readable(const dsl_event* tr, int n, dsl_result** out) override {
+    clear_census();
     if (!have_init) {
       uint8_t tmp[sizeof(init)];
       DSL_TRY(get_initial(tmp, sizeof(init)));
@@ -2635,6 +2696,7 @@ struct BfsEngine : EngineBase {
   // dsl_replay: TraceReplaySearch on the host (replay.hpp).
   int replay(const dsl_event* tr, int n, int minimize, dsl_result** out) override {
     const auto t_start = std::chrono::steady_clock::now();
+    clear_census();
     if (!have_init) {
       uint8_t tmp[sizeof(init)];
       DSL_TRY(get_initial(tmp, sizeof(init)));

@@ -57,6 +57,14 @@ struct DevProg {
   int16_t start, len;
 };
 
+// The engine's watches (dsl_set_watches): top-level predicates with a pool of their own.
+struct WatchList {
+  const dsl_predicate* watches = nullptr;
+  int32_t n = 0;
+  const dsl_predicate* pool = nullptr;
+  int32_t n_pool = 0;
+};
+
 // Device form of SearchSettings/TestSettings. The tri-state precedence of
 // TestSettings.shouldDeliver (TestSettings.java:224-245) is resolved on the host into a
 // boolean matrix deliver[from] bit `to`; timers into timer_mask bit a = deliverTimers(a).
@@ -92,6 +100,13 @@ struct DevSettings {
   // the conditions of the network leaves (behind everything else: the offsets of the fields the
   // kernels without the leaf read are what they were)
   DevRecCond rec_conds[kMaxRecConds];
+  // the watches (dsl_set_watches): predicates that are only counted, programs over the same ops[]
+  // behind those of the invariants, goals and prunes. Behind rec_conds for the same reason; only
+  // k_level<P, false, true> reads them. watch_net: a watch holds a network leaf (its value on the
+  // parent is unknown, so the judge needs the parent row's records: net_needs_row)
+  int32_t n_watch;
+  int32_t watch_net;
+  DevProg watch[DSL_MAX_WATCHES];
 };
 
 // True when no active lane of the wavefront has `p` (device; one thread on the host): the exit of

@@ -243,9 +243,10 @@ static thread_local const dsl_host_comm* g_pending_host_comm = nullptr;
 static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
-int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out) {
+int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out,
+                     const WatchList* watches) {
   std::string why;
-  const int rc = resolve_settings(in, num_nodes, known, out, &why);
+  const int rc = resolve_settings(in, num_nodes, known, out, &why, watches);
   if (rc) set_error(why);
   return rc;
 }
@@ -481,6 +482,30 @@ int dsl_set_initial(dsl_engine* e, const uint8_t* packed, size_t len, int32_t de
 int dsl_set_dropped(dsl_engine* e, const uint64_t* dropped, int32_t n_dropped) {
   if (!e) return DSL_ERR_ARG;
   return e->impl->set_dropped(dropped, n_dropped);
+}
+
+int dsl_set_watches(dsl_engine* e, const dsl_predicate* watches, int32_t n_watches, const dsl_predicate* pool,
+                    int32_t n_pool) {
+  if (!e) return DSL_ERR_ARG;
+  return e->impl->set_watches(watches, n_watches, pool, n_pool);
+}
+
+int dsl_watch_counts(dsl_engine* e, int32_t watch, uint64_t* per_depth, int32_t cap, int32_t* n_levels,
+                     uint64_t* total) {
+  if (!e || cap < 0 || (cap > 0 && !per_depth)) return DSL_ERR_ARG;
+  const auto& census = e->impl->watch_census;
+  if (n_levels) *n_levels = 0;
+  if (total) *total = 0;
+  if (census.empty()) return DSL_OK;  // no watches, or the last call was not a dsl_run: no census
+  if (watch < 0 || watch >= (int32_t)census.size()) {
+    dsl::set_error("dsl_watch_counts: watch " + std::to_string(watch) + " of " + std::to_string(census.size()));
+    return DSL_ERR_ARG;
+  }
+  const auto& c = census[watch];
+  for (int32_t i = 0; i < cap && i < (int32_t)c.size(); i++) per_depth[i] = c[i];
+  if (n_levels) *n_levels = (int32_t)c.size();
+  if (total) *total = e->impl->watch_total[watch];
+  return DSL_OK;
 }
 
 int dsl_get_initial(dsl_engine* e, uint8_t* packed, size_t len) {

@@ -95,6 +95,10 @@ struct LevelCounters {
   unsigned long long unspilled;     // rows k_unspill appended (multi-shard fast path: device count)
   unsigned long long phase[12];     // DSL_PHASES builds only: shader cycles per k_level phase
   unsigned long long phcls[32];     // DSL_PHASES: handler cycles per class [0, 16), wave-passes [16, 32)
+  // newly discovered successors in which each watch held (dsl_set_watches; k_level<P, false, true>
+  // alone adds to them). Behind everything else: no other counter's offset moves. Zeroed with the
+  // set, as every counter is (k_setup, zero_next, the queue's and the end-of-search clears).
+  unsigned long long watch[DSL_MAX_WATCHES];
 };
 
 // Phase timing (instrumented builds, -DDSL_PHASES): wave-level shader-clock deltas per phase of
@@ -679,6 +683,12 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
   const bool find = a.find != 0;
   // per-thread statistics, flushed once per workgroup (no per-wave atomics on shared words)
   uint32_t c_succ = 0, c_new = 0, c_next_work = 0, c_work = 0, c_probe = 0;
+  // the watches' census (FIELD && !ROUTE only): per watch, the wave's count of newly discovered
+  // successors in which it held -- wave-uniform values, added to from ballots at a converged
+  // point of the pass and flushed with one atomic per wave at the kernel's exit; every index is a
+  // compile-time constant, so they are registers (a wave's count of a level is far below 2^32)
+  uint32_t wcnt[DSL_MAX_WATCHES] = {0, 0, 0, 0, 0, 0, 0, 0};
+  const bool watching = FIELD && !ROUTE && set.n_watch != 0 && !find;
   PH_DECL
   PH_CLS_DECL
   if (a.qprev) {
@@ -936,6 +946,7 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
           base += kLevelBlock;
         }
         bool is_valid = false, route = false;
+        uint32_t held = 0;  // bit w: this lane's newly discovered successor holds watch w
         int dest = 0, j = 0, k = 0, tv = 0, tpi = -1;
         uint64_t tkey = ~0ull;  // terminal candidate
         Fp f{0, 0};
@@ -954,7 +965,10 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
           // the network leaves' scan of the parent row, where the judge will ask for it (never on
           // the common path, net_needs_row): here, ahead of the handler, few registers are live
           uint32_t row_hits = 0;
-          if constexpr (FIELD) {
+          if constexpr (FIELD && !ROUTE) {  // ... or a watch holds a network leaf (watch_needs_row)
+            if (net_needs_row(set, a.incremental != 0, 0) || (watching && watch_needs_row(set)))
+              row_hits = row_net_hits<P>(set, w);
+          } else if constexpr (FIELD) {
             if (net_needs_row(set, a.incremental != 0, 0)) row_hits = row_net_hits<P>(set, w);
           }
           // an event that changes neither its node nor the network (a redelivered message most
@@ -1022,6 +1036,11 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
                 view.row_hits = row_hits;
               }
               const int v = judge_view<P, FIELD>(view, prm, set, a.depth, &pi, a.incremental != 0);
+              // the watches of this newly discovered state, whatever its verdict, from the same view
+              // (not in find mode: the level's first run counted them)
+              if constexpr (FIELD && !ROUTE) {
+                if (watching) held = eval_watches<P>(view, prm, set);
+              }
               if (v == V_VALID) {
                 if (route) {
                 } else if (Net<P>::size(w) + dn <= P::kNetCap) {
@@ -1046,6 +1065,13 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
           }
         }
         PH_MARK(4);  // judge (+ divergence wait)
+        if constexpr (FIELD && !ROUTE) {
+          if (watching) {  // the wave is converged here: one ballot and one popcount per watch
+#pragma unroll
+            for (int q = 0; q < DSL_MAX_WATCHES; q++)
+              if (q < set.n_watch) wcnt[q] += (uint32_t)__popcll(__ballot((held >> q) & 1u));
+          }
+        }
         const bool term = tkey != ~0ull;
         if (find) {
           if (term && tkey == a.find_key) a.terms[0] = TerminalRec{tv, tpi, (uint32_t)k, 0u, p0 + j, tkey};
@@ -1141,6 +1167,14 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
                                 : tid == 2 ? &a.ctr->next_work : tid == 3 ? &a.ctr->work_items
                                 : &a.ctr->probes;
       if (t) atomicAdd(dst, t);
+    }
+  }
+  if constexpr (FIELD && !ROUTE) {
+    if (watching) {  // lane q adds the wave's count of watch q: one atomic instruction per wave
+      uint32_t mine = 0;
+#pragma unroll
+      for (int q = 0; q < DSL_MAX_WATCHES; q++) mine = lane == q ? wcnt[q] : mine;
+      if (lane < DSL_MAX_WATCHES && mine) atomicAdd(&a.ctr->watch[lane], (unsigned long long)mine);
     }
   }
   PH_MARK(11);  // the statistics reduction

@@ -698,6 +698,11 @@ DSL_HD uint32_t row_net_hits(const DevSettings& set, const uint32_t* w) {
 DSL_HD bool net_needs_row(const DevSettings& set, bool incremental, int changed) {
   return set.n_net != 0 && !(incremental && changed >= 0 && set.flat);
 }
+// ... and always when a watch (dsl_set_watches) holds a network leaf: a watch's value on the parent
+// is unknown, so its leaf reads the new records, the parent's records and the dropped records. A
+// function of its own, asked only where watches are counted (k_level<P, false, true>): the other
+// callers of net_needs_row compile what they compiled before.
+DSL_HD bool watch_needs_row(const DevSettings& set) { return set.watch_net != 0; }
 // A new record matches, or one of the row's, or a dropped one.
 DSL_HD int eval_net_leaf(const DevPred& pr, const NodeView& v) {
   return (((v.net_hits | v.row_hits) >> pr.pad) & 1u) ? PV_TRUE : PV_FALSE;
@@ -861,6 +866,33 @@ DSL_HD Verdict judge_view(const NodeView& v0, const typename P::Params& prm, con
   }
   if (set.max_depth >= 0 && depth >= set.max_depth) return V_PRUNED;
   return V_VALID;
+}
+
+// The watches (dsl_set_watches) of a view: bit w = watch w holds (true after its negation; a watch
+// that throws does not hold). Evaluation is always full -- P::eval, eval_field_leaf, eval_net_leaf
+// over net_hits | row_hits: the view's state is newly discovered, whatever its verdict, and no
+// watch's value on its parent is known (a parent may hold a watch or not, unlike an invariant), so
+// none of the judge's "keeps the parent's value" shortcuts applies (leaf_unchanged, EvalHeld).
+// The kernel hands over both hit masks (row_hits computed ahead of the handler, net_needs_row with
+// `watches`); host code gets them here, as in judge_view.
+template <class P>
+DSL_HD uint32_t eval_watches(const NodeView& v0, const typename P::Params& prm, const DevSettings& set) {
+  NodeView v = v0;
+  if constexpr (NetPreds<P>::value) {
+    v.dropped = set.dropped();
+    v.ndropped = set.n_dropped;
+  }
+#ifndef __HIP_DEVICE_COMPILE__
+  if (set.n_net) {
+    if (v.sends) v.net_hits |= sends_net_hits<P>(set, static_cast<const typename P::Rec*>(v.sends), v.nsends);
+    v.row_hits = row_net_hits<P>(set, v.base);
+  }
+#endif
+  uint32_t held = 0;
+#pragma nounroll  // one copy of the predicate code; the trip count is wave-uniform
+  for (int w = 0; w < set.n_watch; w++)
+    if (eval_prog<P, true>(set, set.watch[w], v, prm) == PV_TRUE) held |= 1u << w;
+  return held;
 }
 
 // Fills DevPred::reads of every leaf from the protocol's read sets (host, after resolve_settings).

@@ -11,8 +11,10 @@ namespace dsl {
 // TestSettings.shouldDeliver precedence (TestSettings.java:224-245): self-send always; then
 // link override, sender override, receiver override, global networkActive.
 // TestSettings.deliverTimers(a): per-address override else the global flag (:87-89).
+// watches (optional): compiled behind the settings' own predicates into the same ops[] and
+// rec_conds[], with the same checks; a failure leaves *out untouched.
 inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out,
-                            std::string* why_out) {
+                            std::string* why_out, const WatchList* watches = nullptr) {
   DevSettings d{};
   if (num_nodes > DSL_MAX_NODES) return *why_out = "too many nodes", DSL_ERR_ARG;
   if (in.do_checks < DSL_CHECKS_NONE || in.do_checks > DSL_CHECKS_ALL || in.check_sample < 0)
@@ -49,20 +51,22 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
   // predicate trees (leaves + DSL_PRED_AND / _OR / _IMPLIES over pool entries) -> postfix programs
   std::string why;
   int n_rec = 0;  // entries of d.rec_conds in use
+  const dsl_predicate* pool = in.pool;  // the operands of what is being compiled (the watches bring their own)
+  int n_pool = in.n_pool;
   std::function<bool(const dsl_predicate&, int, int*)> emit = [&](const dsl_predicate& p, int level, int* sp) -> bool {
     if (level > 16) return why = "predicate nesting too deep", false;
     const bool comb = p.pred_id == DSL_PRED_AND || p.pred_id == DSL_PRED_OR || p.pred_id == DSL_PRED_IMPLIES;
     if (comb) {
-      if (p.arg0 < 0 || p.arg0 >= in.n_pool || p.arg1 < 0 || p.arg1 >= in.n_pool)
+      if (p.arg0 < 0 || p.arg0 >= n_pool || p.arg1 < 0 || p.arg1 >= n_pool)
         return why = "combinator operand outside dsl_settings.pool", false;
-      if (!emit(in.pool[p.arg0], level + 1, sp)) return false;
+      if (!emit(pool[p.arg0], level + 1, sp)) return false;
       auto push_op = [&](int32_t op) {
         if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
         d.ops[d.n_ops++] = DevPred{op, 0, 0, 0, 0u, 0u};
         return true;
       };
       if (p.pred_id == DSL_PRED_IMPLIES && !push_op(kOpNot)) return false;  // or(negate(a), b)
-      if (!emit(in.pool[p.arg1], level + 1, sp)) return false;
+      if (!emit(pool[p.arg1], level + 1, sp)) return false;
       if (!push_op(p.pred_id == DSL_PRED_AND ? kOpAnd : kOpOr)) return false;
       (*sp)--;
       if (p.negate && !push_op(kOpNot)) return false;
@@ -102,13 +106,13 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
       if (p.arg1 < 1 || p.arg1 > DSL_MAX_NET_CONDS)
         return why = "network predicate: " + std::to_string(p.arg1) + " conditions, outside 1.." +
                      std::to_string(DSL_MAX_NET_CONDS), false;
-      if (p.arg0 < 0 || p.arg0 > in.n_pool || p.arg0 + p.arg1 > in.n_pool)
+      if (p.arg0 < 0 || p.arg0 > n_pool || p.arg0 + p.arg1 > n_pool)
         return why = "network predicate: condition range outside dsl_settings.pool", false;
       if (n_rec + (int)p.arg1 > kMaxRecConds)
         return why = "network predicate: more than " + std::to_string(kMaxRecConds) + " conditions in all", false;
       const int first = n_rec;
       for (int c = 0; c < (int)p.arg1; c++) {
-        const dsl_predicate& q = in.pool[p.arg0 + c];
+        const dsl_predicate& q = pool[p.arg0 + c];
         const std::string at = "network predicate: condition " + std::to_string(c) + " (pool " + std::to_string(p.arg0 + c) + "): ";
         if (q.pred_id != DSL_PRED_REC_COND) return why = at + "not a DSL_PRED_REC_COND", false;
         const uint64_t a0 = (uint64_t)q.arg0, a1 = (uint64_t)q.arg1;
@@ -149,6 +153,23 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
     return why.rfind("predicate not supported", 0) == 0 ? DSL_ERR_UNKNOWN_PREDICATE : DSL_ERR_ARG;
   }
   d.flat = d.n_ops == d.n_inv + d.n_goal + d.n_prune ? 1 : 0;  // one leaf per program
+  if (watches && watches->n != 0) {
+    // behind the three lists (d.flat is theirs alone: a watch tree never switches the flat judge
+    // off); network leaves of watches take the next ordinals of n_net
+    if (watches->n < 0 || watches->n > DSL_MAX_WATCHES)
+      return *why_out = "watches: " + std::to_string(watches->n) + ", outside 0.." + std::to_string(DSL_MAX_WATCHES), DSL_ERR_ARG;
+    if (!watches->watches || watches->n_pool < 0 || watches->n_pool > DSL_MAX_POOL || (watches->n_pool > 0 && !watches->pool))
+      return *why_out = "watches: predicate counts out of range", DSL_ERR_ARG;
+    pool = watches->pool;
+    n_pool = watches->n_pool;
+    const int net0 = d.n_net;
+    if (!compile(watches->watches, watches->n, d.watch)) {
+      *why_out = why;
+      return why.rfind("predicate not supported", 0) == 0 ? DSL_ERR_UNKNOWN_PREDICATE : DSL_ERR_ARG;
+    }
+    d.n_watch = watches->n;
+    d.watch_net = d.n_net > net0 ? 1 : 0;
+  }
   *out = d;
   return DSL_OK;
 }

@@ -409,6 +409,9 @@ class PredicateResult:
         return f'State {verb} "{self.predicate.name}"'
 
 
+_NO_WATCHES = (b"", None, 0, None, 0)  # SearchSettings._encode_watches of a search without watches
+
+
 class SearchSettings:
     """SearchSettings + TestSettings (fluent setters return self)."""
 
@@ -438,6 +441,47 @@ class SearchSettings:
         # dsl_settings.max_terminals: every terminal state of the level that ends a BFS, at most
         # this many listed (SearchResults.terminals()); 0 = only the reported one
         self.max_terminals = 0
+        # watches (dsl_set_watches): predicates that are only counted, per depth, over every state
+        # the search discovers (SearchResults.watchCounts()); they change nothing else
+        self._watches: List[StatePredicate] = []
+
+    def addWatch(self, p: StatePredicate) -> "SearchSettings":
+        """Counts, per depth, the newly discovered states in which ``p`` holds, without ending or
+        cutting the search (an invariant, goal or prune does one or the other). Any predicate the
+        engine accepts; at most 8 per search. BFS on one shard."""
+        if len(self._watches) >= _lib.DSL_MAX_WATCHES:
+            raise ValueError(f"too many watches: at most {_lib.DSL_MAX_WATCHES} in one search")
+        self._watches.append(p)
+        return self
+
+    def clearWatches(self) -> "SearchSettings":
+        self._watches.clear()
+        return self
+
+    def watches(self) -> List[StatePredicate]:
+        return list(self._watches)
+
+    def _encode_watches(self, state: "SearchState") -> tuple:
+        """The C ABI form of the watches, ``(key, watches, n, pool, n_pool)``: two dsl_predicate
+        arrays as dsl_set_watches takes them and a key equal exactly when they are (the engine is
+        told only when it differs from what it holds); the same tuple again while the watches did
+        not change."""
+        if not self._watches:
+            return _NO_WATCHES
+        sig = (state.protocol, tuple(self._watches))
+        cached = self.__dict__.get("_watch_cache")
+        if cached is not None and cached[0] == sig:
+            return cached[1]
+        pool: list = []
+        preds = [p._encode(state, pool) for p in self._watches]
+        if len(pool) > _lib.DSL_MAX_POOL:
+            raise ValueError(f"too many combinator operands and message conditions in the watches: {len(pool)} "
+                             f"pool entries, at most {_lib.DSL_MAX_POOL}")
+        w = (_lib.dsl_predicate * _lib.DSL_MAX_WATCHES)(*preds)
+        pl = (_lib.dsl_predicate * _lib.DSL_MAX_POOL)(*pool)
+        enc = (bytes(w) + bytes(pl), w, len(preds), pl, len(pool))
+        self.__dict__["_watch_cache"] = (sig, enc)
+        return enc
 
     def maxTerminals(self, n: int) -> "SearchSettings":
         """List every terminal state of the level that ends a BFS (all shortest counterexamples,
@@ -559,7 +603,7 @@ class SearchSettings:
     def clone(self) -> "SearchSettings":
         s = SearchSettings()
         s.__dict__.update({k: (v.copy() if isinstance(v, (list, dict)) else v) for k, v in self.__dict__.items()
-                           if k != "_enc_cache"})
+                           if k not in ("_enc_cache", "_watch_cache")})
         return s
 
     # encoding -------------------------------------------------------------------------------
@@ -569,7 +613,7 @@ class SearchSettings:
                 tuple(self._link.items()), tuple(self._sender.items()), tuple(self._receiver.items()),
                 tuple(self._timers_active.items()), tuple(self._invariants), tuple(self._goals), tuple(self._prunes),
                 self.table_log2_slots, self.max_frontier_states, self.memory_budget_bytes, self.do_checks,
-                self.check_sample, self.max_terminals)
+                self.check_sample, self.max_terminals, tuple(self._watches))
 
     def _encode(self, state: "SearchState") -> _lib.dsl_settings:
         """The C ABI form (dsl_settings); the same object again while nothing it reads changed,
@@ -736,6 +780,8 @@ class SearchResults:
                        "first_not_idempotent": None}
         self._terminals: list = []
         self._terminals_total = 0
+        self._watch_counts: List[List[int]] = []
+        self._watch_totals: List[int] = []
 
     def endCondition(self) -> EndCondition:
         return self._end
@@ -785,6 +831,25 @@ class SearchResults:
 
     def exceptionalStates(self) -> List[SearchState]:
         return self._terminals_of(EndCondition.EXCEPTION_THROWN)
+
+    # the watches' census (SearchSettings.addWatch) ----------------------------------------------
+    def watchCounts(self) -> List[List[int]]:
+        """Per watch, in addWatch order, the newly discovered states in which it held at each depth:
+        a list as long as ``per_depth``, index i = depth ``initial_depth + i``. Empty without
+        watches, and after a DFS or a replay."""
+        return [list(c) for c in self._watch_counts]
+
+    def watchTotal(self, i: int) -> int:
+        """All states in which watch ``i`` held, those of a level the time limit cut short included
+        (as ``states`` includes them and ``per_depth`` does not)."""
+        return self._watch_totals[i]
+
+    def watchFirstDepth(self, i: int) -> Optional[int]:
+        """The absolute depth of the first state in which watch ``i`` held; None if none did."""
+        for k, c in enumerate(self._watch_counts[i]):
+            if c:
+                return self.initial_depth + k
+        return None
 
     def statesPerSecond(self) -> float:
         return self.states / self.elapsed_s if self.elapsed_s > 0 else float("inf")
@@ -854,10 +919,22 @@ class Engine:
     def _prepare(self, state: SearchState, settings: SearchSettings):
         lib = self.lib
         enc = settings._encode(state)
+        # the watches: told to the engine only when they differ from what it holds (a search without
+        # watches on an engine without them makes no call). Watches the new settings do not have
+        # leave first, so the new settings are never refused for the old watches' share of the
+        # programs; the new ones follow the settings.
+        wenc = settings._encode_watches(state)
+        held = getattr(self, "_set_watch_key", b"")
+        if wenc[0] != held and held:
+            check(lib.dsl_set_watches(self.handle, None, 0, None, 0), "dsl_set_watches")
+            self._set_watch_key = held = b""
         if enc is not getattr(self, "_set_enc", None):  # the engine keeps the settings it was given
             check(lib.dsl_set_settings(self.handle, ctypes.byref(enc)), "dsl_set_settings")
             self._set_enc = enc
             self._set_dropped = None  # dsl_set_settings re-applies the dropped set the engine holds
+        if wenc[0] != held:
+            check(lib.dsl_set_watches(self.handle, wenc[1], wenc[2], wenc[3], wenc[4]), "dsl_set_watches")
+            self._set_watch_key = wenc[0]
         if state.packed is not None:
             buf = (ctypes.c_uint8 * len(state.packed)).from_buffer_copy(state.packed)
             check(lib.dsl_set_initial(self.handle, buf, len(state.packed), state.depth()), "dsl_set_initial")
@@ -874,7 +951,15 @@ class Engine:
         self._prepare(state, settings)
         res_p = ctypes.POINTER(_lib.dsl_result)()
         check(self.lib.dsl_run(self.handle, ctypes.byref(res_p)), "dsl_run")
-        return self._results(state, settings, res_p)
+        res = self._results(state, settings, res_p)
+        for w in range(len(settings._watches)):  # the census of this run (dsl_watch_counts)
+            n, total = ctypes.c_int32(0), ctypes.c_uint64(0)
+            buf = (ctypes.c_uint64 * max(1, len(res.per_depth)))()
+            check(self.lib.dsl_watch_counts(self.handle, w, buf, len(res.per_depth), ctypes.byref(n),
+                                            ctypes.byref(total)), "dsl_watch_counts")
+            res._watch_counts.append([buf[i] for i in range(min(n.value, len(res.per_depth)))])
+            res._watch_totals.append(total.value)
+        return res
 
     def dfs(self, state: SearchState, settings: Optional[SearchSettings] = None, probes: int = 65536,
             seed: int = 0, max_probes: int = 0, minimize: bool = True, max_trace: int = 0) -> SearchResults:

@@ -43,7 +43,9 @@ extern "C" {
                                terminals, dsl_terminal.
                             Still 6 with DSL_PRED_FIELD and DSL_PRED_NET / _REC_COND: a new dsl_predicate_id
                             changes no struct and adds no entry point; a library without it answers
-                            DSL_ERR_UNKNOWN_PREDICATE */
+                            DSL_ERR_UNKNOWN_PREDICATE.
+                            Still 6 with dsl_set_watches / dsl_watch_counts: two entry points are
+                            added, no struct changes; a caller that never names them runs as before */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -364,6 +366,35 @@ int dsl_set_initial(dsl_engine* e, const uint8_t* packed, size_t len, int32_t de
 int dsl_get_initial(dsl_engine* e, uint8_t* packed, size_t len);
 int dsl_run(dsl_engine* e, dsl_result** out);
 int dsl_progress(dsl_engine* e, uint64_t* states, int32_t* depth);
+
+/* Watches: predicates that are only counted. An invariant, a goal or a prune ends the search or
+ * cuts it; a watch changes nothing (the same states, per_depth, end condition, terminals, traces
+ * and check counts with or without it) and answers "was this situation reached in this search,
+ * how early, how often" -- the coverage side of StatePredicate (T/StatePredicate.java), for which
+ * the reference's tests run one extra goal search per scenario. Every state dsl_run counts in
+ * per_depth is evaluated once against each watch, at the depth where it was first discovered
+ * (BFS.exploreNode's discovered.add, Search.java:468-504): the start state at index 0, then every
+ * newly inserted successor whatever its verdict -- valid, pruned, a goal or invariant terminal, a
+ * maxDepth state. An exceptional successor has no state and is not evaluated. A watch counts when
+ * it is true after its negation; a watch that throws counts as not holding. A watch is any
+ * predicate the settings accept (a named leaf, DSL_PRED_FIELD, DSL_PRED_NET, negate, and / or /
+ * implies trees); the watches share the settings' 64 program steps, 16-deep stack and
+ * DSL_MAX_NET_CONDS_TOTAL network conditions, and whichever of dsl_set_settings / dsl_set_watches
+ * comes second and makes a sum overflow is refused (DSL_ERR_ARG; the engine keeps what it had).
+ * BFS on one shard only: dsl_run with watches and virtual_shards > 1 or world_size > 1 returns
+ * DSL_ERR_ARG before any collective. dsl_run_dfs, dsl_replay and dsl_human_readable_trace ignore
+ * the watches and report none. */
+#define DSL_MAX_WATCHES 8
+/* Replaces the engine's watches (n_watches = 0 clears them). `pool` holds the operands of the
+   watches' combinators and the conditions of their network leaves, indexed as dsl_settings.pool is
+   (n_pool <= DSL_MAX_POOL). The engine keeps them across dsl_set_settings, like the dropped set. */
+int dsl_set_watches(dsl_engine* e, const dsl_predicate* watches, int32_t n_watches,
+                    const dsl_predicate* pool, int32_t n_pool);
+/* The census of the last dsl_run: per_depth[i] (up to cap entries written, *n_levels = the levels
+   there are) = states first discovered at depth initial_depth + i in which watch `watch` held;
+   *total also includes a level cut short by the time limit. n_levels = 0 after any other call. */
+int dsl_watch_counts(dsl_engine* e, int32_t watch, uint64_t* per_depth, int32_t cap,
+                     int32_t* n_levels, uint64_t* total);
 
 /* Random depth-first search (Search.dfs / RandomDFS, Search.java:397-402, :507-583): `probes`
  * independent random walks run concurrently on the device (one per lane), each restarted from

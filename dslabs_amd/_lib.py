@@ -40,7 +40,7 @@ EXPORTED = [
     "dsl_set_settings", "dsl_set_initial", "dsl_get_initial", "dsl_run", "dsl_progress",
     "dsl_kernel_stats", "dsl_result_free", "dsl_destroy", "dsl_last_error", "dsl_create_with_host_comm",
     "dsl_run_dfs", "dsl_replay", "dsl_human_readable_trace", "dsl_set_dropped",
-    "dsl_set_watches", "dsl_watch_counts",
+    "dsl_set_watches", "dsl_watch_counts", "dsl_set_watch_witnesses", "dsl_watch_witness",
 ]
 DSL_ABI_VERSION = 6  # include/dslabs_hip.h; load() refuses a library of another layout
 
@@ -169,6 +169,9 @@ def load() -> ctypes.CDLL:
     lib.dsl_set_watches.argtypes = [ctypes.c_void_p, P(dsl_predicate), ctypes.c_int32, P(dsl_predicate), ctypes.c_int32]
     lib.dsl_watch_counts.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_uint64), ctypes.c_int32,
                                      P(ctypes.c_int32), P(ctypes.c_uint64)]
+    lib.dsl_set_watch_witnesses.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
+    lib.dsl_watch_witness.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_int32), P(dsl_event), ctypes.c_int32,
+                                      P(ctypes.c_int32), P(ctypes.c_uint8), ctypes.c_size_t]
     lib.dsl_run.argtypes = [ctypes.c_void_p, P(P(dsl_result))]
     lib.dsl_run_dfs.argtypes = [ctypes.c_void_p, P(dsl_dfs_config), P(P(dsl_result))]
     lib.dsl_replay.argtypes = [ctypes.c_void_p, P(dsl_event), ctypes.c_int32, ctypes.c_int32, P(P(dsl_result))]

@@ -23,6 +23,7 @@
 #include <cstring>
 #include <memory>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "kernels.hpp"
@@ -88,10 +89,21 @@ struct EngineBase {
   // the census of the last run(): per watch, the count per completed level and the total
   std::vector<std::vector<uint64_t>> watch_census;
   std::vector<uint64_t> watch_total;
+  // the witnesses of the last run() (dsl_set_watch_witnesses): per watch, a state of the first
+  // depth at which it held, with a shortest trace; depth -1 = none. They live and die with the census.
+  struct WatchWitness {
+    int32_t depth = -1;
+    std::vector<dsl_event> trace;
+    std::vector<uint8_t> state;
+  };
+  std::vector<WatchWitness> watch_witness;
   void clear_census() {
     watch_census.clear();
     watch_total.clear();
+    watch_witness.clear();
   }
+  virtual int num_watches() const = 0;
+  virtual int set_watch_witnesses(uint32_t mask) = 0;
   virtual int run(dsl_result** out) = 0;
   virtual int run_dfs(const dsl_dfs_config& c, dsl_result** out) = 0;
   virtual int replay(const dsl_event* trace, int n, int minimize, dsl_result** out) = 0;
@@ -366,8 +378,24 @@ struct BfsEngine : EngineBase {
     }
     const std::vector<dsl_predicate> nw(w, w + n), np(pool, pool + (n ? n_pool : 0));
     const int rc = resolve_all(hset, nw, np);
-    if (rc == DSL_OK) clear_census();
+    if (rc == DSL_OK) {
+      clear_census();
+      witness_mask = 0;  // the requests belong to the watches they were made for
+    }
     return rc;
+  }
+  // The watches that want a witness (dsl_set_watch_witnesses): bit w = watch w.
+  uint32_t witness_mask = 0;
+  int num_watches() const override { return (int)hwatch.size(); }
+  int set_watch_witnesses(uint32_t mask) override {
+    const int n = (int)hwatch.size();
+    if (n < 32 && (mask >> n)) {
+      set_error("watch witnesses: mask 0x" + [&] { char b[16]; snprintf(b, sizeof b, "%x", mask); return std::string(b); }() +
+                " names a watch at or above the " + std::to_string(n) + " set (dsl_set_watches)");
+      return DSL_ERR_ARG;  // the engine keeps the mask it had
+    }
+    witness_mask = mask;
+    return DSL_OK;
   }
   int resolve_all(const dsl_settings& s, const std::vector<dsl_predicate>& w, const std::vector<dsl_predicate>& wp) {
     DevSettings ds;
@@ -708,7 +736,7 @@ struct BfsEngine : EngineBase {
         std::memcpy(&v, set + kCtrSegOff + (size_t)q * kSegStride * 8, 8);
         F += std::min<uint64_t>(v, q_segcap);
       }
-      if (!queue_continues(c, F, flimit, wlimit, room, room_half)) {
+      if (!queue_continues(c, F, flimit, wlimit, room, room_half) || watch_wanted_hit(c, dset.watch_want)) {
         *ran = j + 1;
         break;
       }
@@ -1043,16 +1071,31 @@ struct BfsEngine : EngineBase {
       term_list[i].events.push_back(all[i].rec.event);
     }
     // the chains, one history level at a time for all kept terminals
+    std::vector<uint64_t> parents(n);
+    std::vector<std::vector<uint32_t>*> events(n);
+    for (size_t i = 0; i < n; i++) {
+      parents[i] = all[i].rec.parent;
+      events[i] = &term_list[i].events;
+    }
+    return walk_chains("terminal list", parents, events);
+  }
+  // The parent chains of n states of the newest level (level_size's last entry), one history level
+  // at a time for all of them: parents[i] is state i's parent reference (shard << 48 | row of the
+  // level before), *events[i] holds its last event on entry and its whole trace on return.
+  int walk_chains(const char* what, const std::vector<uint64_t>& parents,
+                  const std::vector<std::vector<uint32_t>*>& events) {
+    const int L = (int)sh.size();
+    const size_t n = parents.size();
     const int nlev = (int)sh[0].level_size.size();
     if (!n || nlev < 3) return DSL_OK;
     DevBufs bufs;
     uint64_t* ref[2] = {nullptr, nullptr};
     DSL_TRY(bufs.get(&ref[0], n * 16));
     DSL_TRY(bufs.get(&ref[1], n * 16));
-    std::vector<uint64_t> hops((size_t)(nlev - 1) * n * 2);  // [0, 2n): the terminals' parents, then one block per level
+    std::vector<uint64_t> hops((size_t)(nlev - 1) * n * 2);  // [0, 2n): the states' parents, then one block per level
     for (size_t i = 0; i < n; i++) {
-      hops[2 * i] = all[i].rec.parent;
-      hops[2 * i + 1] = all[i].rec.event;
+      hops[2 * i] = parents[i];
+      hops[2 * i + 1] = events[i]->back();
     }
     DSL_HIP(hipMemcpyAsync(ref[0], hops.data(), n * 16, hipMemcpyHostToDevice, stream));
     int cur = 0, blk = 1;
@@ -1074,13 +1117,96 @@ struct BfsEngine : EngineBase {
       for (size_t i = 0; i < n; i++) {
         const uint64_t* h = hops.data() + ((size_t)b * n + i) * 2;
         if (h[0] == ~0ull) {
-          set_error("terminal list: a parent chain left the history");
+          set_error(std::string(what) + ": a parent chain left the history");
           return DSL_ERR_ARG;
         }
-        term_list[i].events.push_back((uint32_t)h[1]);
+        events[i]->push_back((uint32_t)h[1]);
       }
-    for (auto& t : term_list) std::reverse(t.events.begin(), t.events.end());
+    for (auto* e : events) std::reverse(e->begin(), e->end());
     return DSL_OK;
+  }
+
+  // ---- a witness of each watch's first hit (dsl_set_watch_witnesses) ----------------------------
+  // After a completed level that counted, for the first time, a watch still in `want`, while the
+  // level's parents are in S.cur: k_watch_witness twice on the stream (the minimum keys, then the
+  // records that carry them), one round trip; per watch the record with the smallest (fingerprint
+  // lo, parent, event) among those of the minimum hi -- the order of terminals(), (hi, lo) -- and the
+  // chains of all of them through the history arena (walk_chains). wit[w] gets the raw event
+  // indices; run_once replays them when the search ends.
+  struct WitnessTrace {
+    int32_t depth = -1;
+    std::vector<uint32_t> events;
+  };
+  int find_witnesses(Shard& S, uint32_t want, int succ_depth, bool incremental, std::vector<WitnessTrace>& wit) {
+    DevBufs bufs;
+    unsigned long long* best = nullptr;  // DSL_MAX_WATCHES words, then the record counter
+    WitnessRec* out = nullptr;
+    uint64_t cap = 64 * (uint64_t)__builtin_popcount(want);
+    DSL_TRY(bufs.get(&best, (DSL_MAX_WATCHES + 1) * 8));
+    DSL_TRY(bufs.get(&out, cap * sizeof(WitnessRec)));
+    DSL_HIP(hipMemsetAsync(best, 0, (DSL_MAX_WATCHES + 1) * 8, stream));
+    WitnessArgs<P> a{};
+    a.cur = S.cur;
+    a.cur_fp = S.cur_fp;
+    const int per = mat_per_max<P>();
+    a.segs.n = (int32_t)S.seg_cnt.size();
+    a.segs.pb = per;
+    for (int q = 0; q < a.segs.n; q++) {
+      a.segs.base[q] = S.seg_base[q];
+      a.segs.cnt[q] = S.seg_cnt[q];
+      a.segs.chunk0[q + 1] = a.segs.chunk0[q] + (S.seg_cnt[q] + per - 1) / per;
+    }
+    a.incremental = incremental ? 1 : 0;
+    a.want = want;
+    a.best = best;
+    a.out = out;
+    a.cap = cap;
+    a.n_out = best + DSL_MAX_WATCHES;
+    const uint64_t nchunks = a.segs.chunk0[a.segs.n];
+    const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((nchunks + kBlock / 64 - 1) / (kBlock / 64), 4096));
+    const size_t lds = (size_t)(kBlock / 64) * per * NW * 4;
+    unsigned long long h[DSL_MAX_WATCHES + 1] = {};
+    std::vector<WitnessRec> recs;
+    for (int pass = 0; pass < 2; pass++) {  // the second only when the records ran past their room
+      for (a.find = pass; a.find < 2; a.find++) {
+        hipLaunchKernelGGL(k_watch_witness<P>, dim3(blocks), dim3(kBlock), lds, stream, a, prm, dset);
+        DSL_HIP(hipGetLastError());
+      }
+      DSL_HIP(hipMemcpyAsync(h, best, sizeof(h), hipMemcpyDeviceToHost, stream));
+      recs.resize(a.cap);
+      DSL_HIP(hipMemcpyAsync(recs.data(), a.out, a.cap * sizeof(WitnessRec), hipMemcpyDeviceToHost, stream));
+      DSL_TRY(hsync());
+      if (h[DSL_MAX_WATCHES] <= a.cap) break;
+      if (pass) {
+        set_error("watch witness: the record pass overflowed at its exact size");
+        return DSL_ERR_ARG;
+      }
+      a.cap = h[DSL_MAX_WATCHES];
+      DSL_TRY(bufs.get(&a.out, a.cap * sizeof(WitnessRec)));
+      DSL_HIP(hipMemsetAsync(a.n_out, 0, 8, stream));
+    }
+    recs.resize(h[DSL_MAX_WATCHES]);
+    std::vector<uint64_t> parents;
+    std::vector<std::vector<uint32_t>*> events;
+    for (int w = 0; w < DSL_MAX_WATCHES; w++) {
+      if (!((want >> w) & 1u)) continue;
+      const WitnessRec* pick = nullptr;
+      for (const auto& r : recs) {
+        if ((int)r.watch != w || r.fp.hi != ~(uint64_t)h[w]) continue;
+        if (!pick || std::make_tuple(r.fp.lo, r.parent, r.event) < std::make_tuple(pick->fp.lo, pick->parent, pick->event))
+          pick = &r;
+      }
+      if (!pick) {
+        set_error("watch witness: no successor of depth " + std::to_string(succ_depth) + " carries watch " +
+                  std::to_string(w) + "'s minimum key");
+        return DSL_ERR_ARG;
+      }
+      wit[w].depth = succ_depth;
+      wit[w].events.assign(1, pick->event);
+      parents.push_back(((uint64_t)S.gid << 48) | pick->parent);
+      events.push_back(&wit[w].events);
+    }
+    return walk_chains("watch witness", parents, events);
   }
 
   // ---- sharded levels: the fast path ----------------------------------------------
@@ -1809,6 +1935,15 @@ struct BfsEngine : EngineBase {
       const uint32_t held = eval_watches<P>(v0, prm, dset);
       for (int w = 0; w < n_watch; w++) census[w][0] = census_total[w] = (held >> w) & 1u;
     }
+    // the witnesses of this attempt (a restarted search finds them again): a watch that holds on
+    // the start state has it as its witness, with an empty trace; the others wait in watch_want
+    std::vector<WitnessTrace> wit(n_watch);
+    dset.watch_want = n_watch ? witness_mask : 0u;
+    for (int w = 0; w < n_watch; w++)
+      if (((dset.watch_want >> w) & 1u) && census[w][0]) {
+        wit[w].depth = init_depth;
+        dset.watch_want &= ~(1u << w);
+      }
     for (auto& S : sh) {
       // one k_setup per shard: zeroes its table and counters; seeds the initial state's owner (or
       // every shard while small levels are replicated)
@@ -2302,6 +2437,15 @@ struct BfsEngine : EngineBase {
           Shard& S = sh[l];
           S.level_size.push_back(span[l]);
         }
+        // a wanted watch's first non-zero count in a completed level: its witness, while the level's
+        // parents are still in S.cur (a level the deadline cut short is not enumerated)
+        if (dset.watch_want && !level_tup && watch_wanted_hit(sh[0].lc, dset.watch_want)) {
+          uint32_t hit = 0;
+          for (int w = 0; w < n_watch; w++)
+            if (((dset.watch_want >> w) & 1u) && sh[0].lc.watch[w]) hit |= 1u << w;
+          DSL_TRY(find_witnesses(sh[0], hit, depth, depth - 1 > init_depth, wit));
+          dset.watch_want &= ~hit;  // later levels queue as before
+        }
         const double lms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - lt0).count();
         level_ms_max = std::max(level_ms_max, lms);
         // the cost model (auto replicate_below): c from levels in the throughput regime, X from the
@@ -2497,6 +2641,21 @@ struct BfsEngine : EngineBase {
     *out = r;
     watch_census = std::move(census);
     watch_total = std::move(census_total);
+    // the witnesses: their events replayed on the host, as the terminal's are
+    watch_witness.assign(n_watch, WatchWitness{});
+    for (int w = 0; w < n_watch; w++) {
+      if (wit[w].depth < 0) continue;
+      WatchWitness& o = watch_witness[w];
+      o.depth = wit[w].depth;
+      o.trace.resize(wit[w].events.size());
+      typename P::State ws = init, wn;
+      for (size_t i = 0; i < wit[w].events.size(); i++) {
+        describe_event<P>(ws.w, (int)wit[w].events[i], prm, dset, &o.trace[i]);
+        full_step<P>(ws.w, (int)wit[w].events[i], wn.w, prm, dset);
+        ws = wn;
+      }
+      o.state.assign((const uint8_t*)&ws, (const uint8_t*)&ws + sizeof(init));
+    }
     return DSL_OK;
   }
 

@@ -508,6 +508,31 @@ int dsl_watch_counts(dsl_engine* e, int32_t watch, uint64_t* per_depth, int32_t 
   return DSL_OK;
 }
 
+int dsl_set_watch_witnesses(dsl_engine* e, uint32_t mask) {
+  if (!e) return DSL_ERR_ARG;
+  return e->impl->set_watch_witnesses(mask);
+}
+
+int dsl_watch_witness(dsl_engine* e, int32_t watch, int32_t* depth, dsl_event* trace, int32_t cap, int32_t* trace_len,
+                      uint8_t* state, size_t len) {
+  if (!e || cap < 0 || (cap > 0 && !trace)) return DSL_ERR_ARG;
+  if (watch < 0 || watch >= e->impl->num_watches()) {
+    dsl::set_error("dsl_watch_witness: watch " + std::to_string(watch) + " of " +
+                   std::to_string(e->impl->num_watches()));
+    return DSL_ERR_ARG;
+  }
+  if (depth) *depth = -1;
+  if (trace_len) *trace_len = 0;
+  const auto& wit = e->impl->watch_witness;
+  if (watch >= (int32_t)wit.size() || wit[watch].depth < 0) return DSL_OK;  // no witness
+  const auto& w = wit[watch];
+  if (depth) *depth = w.depth;
+  for (int32_t i = 0; i < cap && i < (int32_t)w.trace.size(); i++) trace[i] = w.trace[i];
+  if (trace_len) *trace_len = (int32_t)w.trace.size();
+  if (state && len == w.state.size()) std::memcpy(state, w.state.data(), len);
+  return DSL_OK;
+}
+
 int dsl_get_initial(dsl_engine* e, uint8_t* packed, size_t len) {
   if (!e || !packed) return DSL_ERR_ARG;
   return e->impl->get_initial(packed, len);

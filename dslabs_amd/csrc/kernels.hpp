@@ -567,6 +567,15 @@ __host__ __device__ inline bool queue_continues(const LevelCounters& c, uint64_t
          c.next_work <= wlimit &&
          c.cum_before + c.new_states + 2 * est <= room34 && c.cum_before + c.new_states + est <= room_half;
 }
+// ... and, in a watched search, after a level that counted a watch still waiting for its witness
+// (DevSettings::watch_want): the witness pass re-expands that level's parents, which the next
+// queued level would overwrite (the queue ping-pongs the two frontier buffers). Asked by
+// k_level<P, false, true> alone, and by the host's mirror walk (BfsEngine::enqueue_queue).
+__host__ __device__ inline bool watch_wanted_hit(const LevelCounters& c, uint32_t want) {
+  unsigned long long any = 0;
+  for (int q = 0; q < DSL_MAX_WATCHES; q++) any |= ((want >> q) & 1u) ? c.watch[q] : 0ull;
+  return any != 0;
+}
 
 // Copies n16 16-byte units from global memory to LDS with LDS-DMA: wave w issues units
 // [64 (w + 4 r), +64) for r = 0, 1, ...; the destination of one wave-instruction is its
@@ -711,6 +720,9 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
         s_segs.pb = pb;
         s_segs.chunk0[0] = 0;
         s_stop = queue_continues(*a.qprev, F, a.qflimit, a.qwlimit, a.qroom, a.qroom_half) ? 0 : 1;
+        if constexpr (FIELD && !ROUTE) {  // a wanted watch's first hit: the host takes its witness first
+          if (set.watch_want && watch_wanted_hit(*a.qprev, set.watch_want)) s_stop = 1;
+        }
       }
     }
   } else {
@@ -1883,6 +1895,169 @@ __global__ void __launch_bounds__(kBlock) k_list_terminals(ListArgs<P> a, typena
         a.out[slot] = ListedTerminal{TerminalRec{tv, tpi, (uint32_t)k, 0u, p0 + (uint64_t)j, term_key(tv, f.hi)}, f};
     }
     __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
+  }
+}
+
+// ---- a witness of each watch's first hit (dsl_set_watch_witnesses) ---------------------------------
+// Runs after a completed level in which a watch that wants a witness was counted for the first
+// time, over that level's frontier (still in `cur`): the level's expansion again, wave by wave as
+// k_list_terminals does it, with every successor taken as new. This is sound for the same reason:
+// a successor first discovered at an earlier depth had its watches evaluated there and the watch
+// did not hold, or this would not be the first level with a non-zero count -- so every successor of
+// this level in which the watch holds was newly discovered in it, and the visited table is neither
+// read nor written. Exceptional successors have no state and are never counted: skipped.
+// Two launches on one stream, no host round trip between them:
+//   find = 0: per wanted watch, the minimum of f.hi over the successors in which it holds -- a
+//     wave keeps its running minimum (wave-uniform, constant indices) and folds it at its exit with
+//     one 64-bit atomicMax of the complement into best[w] (zeroed; lane w issues watch w's);
+//   find = 1: a lane whose successor holds watch w and whose f.hi equals ~best[w] appends
+//     {parent, event, w, fingerprint} to `out` (one returning atomic per wave and watch). A state
+//     has one record per (parent, event) that reaches it; the host takes the smallest (lo, parent,
+//     event), and runs this launch again at the exact size if the counter ran past `cap`.
+// A kernel of its own: k_level's register allocation must not move for a pass that runs at most
+// once per watch.
+struct WitnessRec {
+  uint64_t parent;  // index of the parent in the current frontier
+  uint32_t event;   // event index within the parent's enabled events
+  uint32_t watch;
+  Fp fp;
+};
+
+template <class P>
+struct WitnessArgs {
+  const uint32_t* cur;
+  const Fp* cur_fp;
+  SegTable segs;               // row ranges of the frontier; pb = parents per wave chunk, chunk0 in those chunks
+  int32_t incremental;
+  int32_t find;
+  uint32_t want;               // the watches selected in this pass
+  unsigned long long* best;    // DSL_MAX_WATCHES words: ~(minimum f.hi), 0 = none yet
+  WitnessRec* out;
+  uint64_t cap;
+  unsigned long long* n_out;   // records appended (past cap: not written)
+};
+
+template <class P>
+__global__ void __launch_bounds__(kBlock) k_watch_witness(WitnessArgs<P> a, typename P::Params prm, DevSettings set) {
+  constexpr int NW = Layout<P>::kWords;
+  constexpr int PMAX = mat_per_max<P>();
+  constexpr int NWV = kBlock / 64;
+  __shared__ uint32_t s_nodew[kBlock * P::kNodeWords];
+  __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kBlock * P::kMaxSends : 1];
+  __shared__ int s_off[NWV][PMAX + 1];
+  extern __shared__ __align__(16) uint32_t s_mrows[];  // NWV x PMAX parent rows
+  const int lane = __lane_id(), wid = threadIdx.x >> 6;
+  uint32_t* wrows = s_mrows + wid * PMAX * NW;
+  int* off = s_off[wid];
+  const int per = a.segs.pb;  // <= PMAX (host)
+  const uint64_t nchunks = a.segs.chunk0[a.segs.n];
+  const bool find = a.find != 0;
+  // per watch (wave-uniform, constant indices: registers): find = 0 the wave's minimum so far,
+  // find = 1 the key to look for
+  unsigned long long wkey[DSL_MAX_WATCHES];
+  uint32_t seen = 0;  // find = 0: the watches with a candidate in this wave
+#pragma unroll
+  for (int q = 0; q < DSL_MAX_WATCHES; q++) wkey[q] = find ? ~a.best[q] : ~0ull;
+  const bool need_row = net_needs_row(set, a.incremental != 0, 0) || watch_needs_row(set);
+  for (uint64_t c = (uint64_t)blockIdx.x * NWV + wid; c < nchunks; c += (uint64_t)gridDim.x * NWV) {
+    int sq = 0;
+    while (sq + 1 < a.segs.n && c >= a.segs.chunk0[sq + 1]) sq++;
+    const uint64_t r0 = (c - a.segs.chunk0[sq]) * (uint64_t)per;
+    const uint64_t p0 = a.segs.base[sq] + r0;
+    const int nr = (int)min<uint64_t>((uint64_t)per, a.segs.cnt[sq] - r0);
+    // the chunk's rows (contiguous) into LDS with LDS-DMA, 64 16-byte units per wave-instruction
+    const int n16 = nr * (NW / 4);
+    const uint4* src = reinterpret_cast<const uint4*>(a.cur + p0 * NW);
+    for (int b = 0; b < n16; b += 64)
+      if (b + lane < n16)
+        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + b + lane),
+                                         (__attribute__((address_space(3))) void*)(wrows + 4 * b), 16, 0, 0);
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // enabled events per parent, and their exclusive scan
+    int x = 0;
+    if (lane < nr) x = count_events<P>(wrows + lane * NW, prm, set);
+    x = (int)wave_incl_sum((uint32_t)x);
+    const int total = (int)rl32((uint32_t)x, 63);
+    if (lane < nr) off[lane + 1] = x;
+    if (lane == 0) off[0] = 0;
+    __builtin_amdgcn_wave_barrier();
+    for (int t0 = 0; t0 < total; t0 += 64) {
+      const int t = t0 + lane;
+      uint32_t held = 0;
+      int k = 0, j = 0;
+      Fp f{0, 0};
+      if (t < total) {
+        // the parent of item t: the last j with off[j] <= t
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (off[mid] <= t) lo = mid;
+          else hi = mid - 1;
+        }
+        j = lo;
+        k = t - off[j];
+        const uint32_t* w = wrows + j * NW;
+        Delta<P> d;
+        d.node = 0;
+        d.out.n = 0;
+        d.keep = 0;
+        uint32_t row_hits = 0;  // as k_level's, with watches
+        if (need_row) row_hits = row_net_hits<P>(set, w);
+        const int rc = delta_step<P>(w, k, d, prm, set);
+        if (rc == STEP_OK) {
+          const int dn = delta_new_count<P>(d);
+          // a successor that changes neither its node nor the network is its parent: not new
+          const bool noop = dn == 0 && same_words<P::kNodeWords>(d.nw, w + d.node * P::kNodeWords);
+          if (!noop) {
+            f = delta_fingerprint<P>(w, a.cur_fp[p0 + j], d);
+            uint32_t* my_nw = s_nodew + threadIdx.x * P::kNodeWords;
+#pragma unroll
+            for (int i = 0; i < P::kNodeWords; i++) my_nw[i] = d.nw[i];
+            NodeView view{w, P::kNodeWords, d.node, my_nw};
+            if constexpr (NetPreds<P>::value) {
+              typename P::Rec* ms = s_sends + threadIdx.x * P::kMaxSends;
+              int n = 0;
+#pragma unroll
+              for (int i = 0; i < P::kMaxSends; i++)
+                if ((d.keep >> i) & 1u) ms[n++] = d.out.r[i];
+              view.sends = ms;
+              view.nsends = n;
+            }
+            if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
+            view.row_hits = row_hits;
+            held = eval_watches<P>(view, prm, set) & a.want;
+          }
+        }  // exceptional successors are never counted; STEP_OVERFLOW: the level reported it
+      }
+      // the wave is converged here
+#pragma unroll
+      for (int q = 0; q < DSL_MAX_WATCHES; q++) {
+        if (!((a.want >> q) & 1u)) continue;
+        const bool h = (held >> q) & 1u;
+        if (!find) {
+          // the wave's minimum key: a scalar walk over the (few) holding lanes
+          for (unsigned long long r = __ballot(h); r; r &= r - 1) {
+            const unsigned long long y = rl64(f.hi, __ffsll((long long)r) - 1);
+            wkey[q] = y < wkey[q] ? y : wkey[q];
+            seen |= 1u << q;
+          }
+        } else {
+          const bool hit = h && f.hi == wkey[q];
+          if (__ballot(hit)) {
+            const unsigned long long slot = wave_reserve(a.n_out, hit);
+            if (hit && slot < a.cap) a.out[slot] = WitnessRec{p0 + (uint64_t)j, (uint32_t)k, (uint32_t)q, f};
+          }
+        }
+      }
+    }
+    __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
+  }
+  if (!find) {  // lane q folds the wave's minimum of watch q: one atomic instruction per wave
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int q = 0; q < DSL_MAX_WATCHES; q++) mine = (lane == q && ((seen >> q) & 1u)) ? ~wkey[q] : mine;
+    if (lane < DSL_MAX_WATCHES && mine) atomicMax(&a.best[lane], mine);
   }
 }
 

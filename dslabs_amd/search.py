@@ -444,19 +444,29 @@ class SearchSettings:
         # watches (dsl_set_watches): predicates that are only counted, per depth, over every state
         # the search discovers (SearchResults.watchCounts()); they change nothing else
         self._watches: List[StatePredicate] = []
+        # per watch: the search also returns a witness state of its first hit (dsl_set_watch_witnesses)
+        self._witness: List[bool] = []
 
-    def addWatch(self, p: StatePredicate) -> "SearchSettings":
+    def addWatch(self, p: StatePredicate, witness: bool = False) -> "SearchSettings":
         """Counts, per depth, the newly discovered states in which ``p`` holds, without ending or
         cutting the search (an invariant, goal or prune does one or the other). Any predicate the
-        engine accepts; at most 8 per search. BFS on one shard."""
+        engine accepts; at most 8 per search. BFS on one shard. ``witness=True`` also asks for one
+        state of the first depth at which ``p`` held, with a shortest trace
+        (SearchResults.watchWitness): what a goal search's goalMatchingState() gives."""
         if len(self._watches) >= _lib.DSL_MAX_WATCHES:
             raise ValueError(f"too many watches: at most {_lib.DSL_MAX_WATCHES} in one search")
         self._watches.append(p)
+        self._witness.append(bool(witness))
         return self
 
     def clearWatches(self) -> "SearchSettings":
         self._watches.clear()
+        self._witness.clear()
         return self
+
+    def _witness_mask(self) -> int:
+        """dsl_set_watch_witnesses' mask: bit w = watch w wants a witness."""
+        return sum(1 << w for w, f in enumerate(self._witness) if f)
 
     def watches(self) -> List[StatePredicate]:
         return list(self._watches)
@@ -613,7 +623,7 @@ class SearchSettings:
                 tuple(self._link.items()), tuple(self._sender.items()), tuple(self._receiver.items()),
                 tuple(self._timers_active.items()), tuple(self._invariants), tuple(self._goals), tuple(self._prunes),
                 self.table_log2_slots, self.max_frontier_states, self.memory_budget_bytes, self.do_checks,
-                self.check_sample, self.max_terminals, tuple(self._watches))
+                self.check_sample, self.max_terminals, tuple(self._watches), tuple(self._witness))
 
     def _encode(self, state: "SearchState") -> _lib.dsl_settings:
         """The C ABI form (dsl_settings); the same object again while nothing it reads changed,
@@ -782,6 +792,7 @@ class SearchResults:
         self._terminals_total = 0
         self._watch_counts: List[List[int]] = []
         self._watch_totals: List[int] = []
+        self._witnesses: List[Optional[SearchState]] = []
 
     def endCondition(self) -> EndCondition:
         return self._end
@@ -850,6 +861,17 @@ class SearchResults:
             if c:
                 return self.initial_depth + k
         return None
+
+    def watchWitness(self, i: int) -> Optional[SearchState]:
+        """The witness of watch ``i`` (``addWatch(p, witness=True)``): the state with the smallest
+        fingerprint among those first discovered at ``watchFirstDepth(i)`` in which the watch held,
+        with a shortest trace to it -- independent of arrival order, buffer sizes and restarts, and
+        usable as the start of the next ``Engine.bfs``. None when none was requested, the watch
+        never held in a completed level, or the result is a DFS's or a replay's."""
+        n = len(self._watch_counts) if self._watch_counts else _lib.DSL_MAX_WATCHES
+        if not 0 <= i < n:
+            raise ValueError(f"watchWitness: watch {i} of {n}")
+        return self._witnesses[i] if i < len(self._witnesses) else None
 
     def statesPerSecond(self) -> float:
         return self.states / self.elapsed_s if self.elapsed_s > 0 else float("inf")
@@ -928,6 +950,7 @@ class Engine:
         if wenc[0] != held and held:
             check(lib.dsl_set_watches(self.handle, None, 0, None, 0), "dsl_set_watches")
             self._set_watch_key = held = b""
+            self._set_witness_mask = 0  # dsl_set_watches resets it
         if enc is not getattr(self, "_set_enc", None):  # the engine keeps the settings it was given
             check(lib.dsl_set_settings(self.handle, ctypes.byref(enc)), "dsl_set_settings")
             self._set_enc = enc
@@ -935,6 +958,11 @@ class Engine:
         if wenc[0] != held:
             check(lib.dsl_set_watches(self.handle, wenc[1], wenc[2], wenc[3], wenc[4]), "dsl_set_watches")
             self._set_watch_key = wenc[0]
+            self._set_witness_mask = 0
+        # the witness requests: only with watches, and only when they differ from what the engine holds
+        if settings._watches and settings._witness_mask() != getattr(self, "_set_witness_mask", 0):
+            check(lib.dsl_set_watch_witnesses(self.handle, settings._witness_mask()), "dsl_set_watch_witnesses")
+            self._set_witness_mask = settings._witness_mask()
         if state.packed is not None:
             buf = (ctypes.c_uint8 * len(state.packed)).from_buffer_copy(state.packed)
             check(lib.dsl_set_initial(self.handle, buf, len(state.packed), state.depth()), "dsl_set_initial")
@@ -959,7 +987,25 @@ class Engine:
                                             ctypes.byref(total)), "dsl_watch_counts")
             res._watch_counts.append([buf[i] for i in range(min(n.value, len(res.per_depth)))])
             res._watch_totals.append(total.value)
+        if any(settings._witness):  # the witnesses of this run (dsl_watch_witness)
+            base = state.trace() if state.packed is not None else []
+            nb = self.state_bytes()
+            for w, want in enumerate(settings._witness):
+                res._witnesses.append(self._witness_state(w, len(res.per_depth), nb, base, state._dropped) if want
+                                      else None)
         return res
+
+    def _witness_state(self, w: int, cap: int, nb: int, base: List[str], dropped) -> Optional[SearchState]:
+        depth, n = ctypes.c_int32(-1), ctypes.c_int32(0)
+        tr = (_lib.dsl_event * max(1, cap))()
+        buf = (ctypes.c_uint8 * nb)()
+        check(self.lib.dsl_watch_witness(self.handle, w, ctypes.byref(depth), tr, cap, ctypes.byref(n), buf, nb),
+              "dsl_watch_witness")
+        if depth.value < 0:
+            return None
+        raw = [_lib.dsl_event.from_buffer_copy(tr[i]) for i in range(min(n.value, cap))]
+        return SearchState(self.protocol, bytes(buf), depth.value, base + [self.protocol.render_event(e) for e in raw],
+                           raw, dropped)
 
     def dfs(self, state: SearchState, settings: Optional[SearchSettings] = None, probes: int = 65536,
             seed: int = 0, max_probes: int = 0, minimize: bool = True, max_trace: int = 0) -> SearchResults:

@@ -45,7 +45,8 @@ extern "C" {
                             changes no struct and adds no entry point; a library without it answers
                             DSL_ERR_UNKNOWN_PREDICATE.
                             Still 6 with dsl_set_watches / dsl_watch_counts: two entry points are
-                            added, no struct changes; a caller that never names them runs as before */
+                            added, no struct changes; a caller that never names them runs as before.
+                            Still 6 with dsl_set_watch_witnesses / dsl_watch_witness: the same again */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -395,6 +396,27 @@ int dsl_set_watches(dsl_engine* e, const dsl_predicate* watches, int32_t n_watch
    *total also includes a level cut short by the time limit. n_levels = 0 after any other call. */
 int dsl_watch_counts(dsl_engine* e, int32_t watch, uint64_t* per_depth, int32_t cap,
                      int32_t* n_levels, uint64_t* total);
+/* Witnesses: for every watch that asks for one, dsl_run also returns one state of the first depth
+ * at which the watch held in a completed level, with a shortest trace to it (depth -
+ * initial_depth events) -- what the reference's goalMatchingState() gives a goal search, without
+ * the goal search; the state can be the dsl_set_initial of the next stage. Among the states first
+ * discovered at that depth in which the watch held it is the one with the smallest fingerprint,
+ * in the (hi, lo) order of dsl_result.terminals, so it depends on no arrival order, buffer size or
+ * restart; a state with two parents may be traced through either. A watch that holds on the start
+ * state has the start state as its witness, with an empty trace. An exceptional successor is never
+ * a witness, and a level cut short by the time limit gives none. Nothing else changes: the same
+ * states, per_depth, end condition, terminals, traces, check counts and census with or without
+ * witness requests. The level that ends a search with a terminal is a completed level.
+ * Bit w of `mask` asks for a witness of watch w. A bit at or above the number of watches is
+ * DSL_ERR_ARG (named in dsl_last_error; the engine keeps the mask it had). dsl_set_watches resets
+ * the mask to 0. */
+int dsl_set_watch_witnesses(dsl_engine* e, uint32_t mask);
+/* The witness of watch `watch` from the last dsl_run: *depth = its absolute depth, or -1 when there
+   is none (not requested, never held in a completed level, or the last call was not a dsl_run); up
+   to cap events written to `trace`, *trace_len = the full length; `state` is filled when len is the
+   packed state's size. A null engine or a watch index outside the watches set is DSL_ERR_ARG. */
+int dsl_watch_witness(dsl_engine* e, int32_t watch, int32_t* depth, dsl_event* trace, int32_t cap,
+                      int32_t* trace_len, uint8_t* state, size_t len);
 
 /* Random depth-first search (Search.dfs / RandomDFS, Search.java:397-402, :507-583): `probes`
  * independent random walks run concurrently on the device (one per lane), each restarted from

@@ -24,6 +24,7 @@
 #include <memory>
 #include <string>
 #include <tuple>
+#include <type_traits>
 #include <vector>
 
 #include "kernels.hpp"
@@ -50,6 +51,17 @@ int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), 
     int r_ = (x);      \
     if (r_) return r_; \
   } while (0)
+
+using Clock = std::chrono::steady_clock;
+inline double ms_since(Clock::time_point t) {
+  return std::chrono::duration<double, std::milli>(Clock::now() - t).count();
+}
+
+// The end condition a terminal verdict (V_TERM_*) gives.
+inline int end_condition_of(int verdict) {
+  return verdict == V_TERM_EXCEPTION ? DSL_EXCEPTION_THROWN
+         : verdict == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED : DSL_GOAL_FOUND;
+}
 
 // Collectives across ranks (one local shard per rank). RCCL / caller transports in engine.hip.
 struct Comm {
@@ -462,6 +474,77 @@ struct BfsEngine : EngineBase {
     std::memcpy(p, &init, len);
     return DSL_OK;
   }
+  int ensure_init() {  // the protocol's own initial state unless the caller set one
+    uint8_t tmp[sizeof(init)];
+    return have_init ? DSL_OK : get_initial(tmp, sizeof(init));
+  }
+  int ensure_stream() {
+    if (stream) return DSL_OK;
+    if (cfg.device >= 0) DSL_HIP(hipSetDevice(cfg.device));
+    DSL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
+    DSL_HIP(hipEventCreate(&ev0));
+    DSL_HIP(hipEventCreate(&ev1));
+    return DSL_OK;
+  }
+
+  // Event indices replayed on the host from the initial state with the same transition code:
+  // out[i] describes event i at the state it leaves; the end state comes back.
+  typename P::State replay_events(const std::vector<uint32_t>& events, dsl_event* out) const {
+    typename P::State s = init, n;
+    for (size_t i = 0; i < events.size(); i++) {
+      describe_event<P>(s.w, (int)events[i], prm, dset, &out[i]);
+      full_step<P>(s.w, (int)events[i], n.w, prm, dset);
+      s = n;
+    }
+    return s;
+  }
+
+  // The current frontier's row ranges as a kernel's segment table, in chunks of `per` parents.
+  static SegTable frontier_segs(const Shard& S, int per) {
+    SegTable t{};
+    t.n = (int32_t)S.seg_cnt.size();
+    t.pb = per;
+    t.chunk0[0] = 0;
+    for (int q = 0; q < t.n; q++) {
+      t.base[q] = S.seg_base[q];
+      t.cnt[q] = S.seg_cnt[q];
+      t.chunk0[q + 1] = t.chunk0[q] + (S.seg_cnt[q] + per - 1) / per;
+    }
+    return t;
+  }
+  // The next frontier becomes the current one (flip: which buffer of each pair is `cur`).
+  static void swap_frontier(Shard& S) {
+    std::swap(S.cur, S.next);
+    std::swap(S.cur_cap, S.next_cap);
+    std::swap(S.cur_fp, S.next_fp);
+    std::swap(S.curfp_cap, S.nextfp_cap);
+    S.flip = !S.flip;
+  }
+  // What every k_level launch over shard S sets alike: the frontier in and out (flip: a queue's
+  // odd levels run next -> cur) with history level `lev` for the successors' parents and events,
+  // the shards and the terminal records; a level of the search also the visited table, the spill
+  // list and the deadline (find mode probes no table, appends no row and has no deadline).
+  LevelArgs<P> level_args(const Shard& S, bool flip, size_t lev, bool find, bool rep = false) const {
+    LevelArgs<P> a{};
+    a.cur = flip ? S.next : S.cur;
+    a.cur_fp = flip ? S.next_fp : S.cur_fp;
+    a.next = flip ? S.cur : S.next;
+    a.next_fp = flip ? S.cur_fp : S.next_fp;
+    a.next_parent = S.hpar[lev];
+    a.next_event = S.hev[lev];
+    a.terms = S.terms;
+    a.term_cap = find ? 1 : term_cap;
+    a.W = W;
+    a.me = S.gid;
+    if (find) return a;
+    a.table = tbl;
+    a.table.slots = S.table;
+    a.spill = S.spill;
+    a.spill_cap = S.spill_cap;
+    a.t0_rt = t0_rt;
+    a.budget_rt = level_budget(rep);
+    return a;
+  }
 
   template <class T>
   int grow(T** ptr, uint64_t* cap, uint64_t need, bool keep, uint64_t keep_elems) {
@@ -503,10 +586,13 @@ struct BfsEngine : EngineBase {
     return DSL_OK;
   }
 
-  int global_sum(std::vector<uint64_t>& v) {
+  // T: a struct of uint64_t members alone (FrontierTotals, LevelTotals), summed word by word.
+  template <class T>
+  int global_sum(T& v) {
+    static_assert(std::is_standard_layout<T>::value && sizeof(T) % 8 == 0 && alignof(T) == 8, "words of uint64_t");
     if (!comm) return DSL_OK;
     stats.host_syncs++;
-    return comm->allreduce_u64(v.data(), (int)v.size(), false, stream);
+    return comm->allreduce_u64(reinterpret_cast<uint64_t*>(&v), (int)(sizeof(T) / 8), false, stream);
   }
 
   // One all-to-all round: local shard l sends sb[l][d] bytes at send[l] + so[l][d] to shard d and
@@ -665,24 +751,15 @@ struct BfsEngine : EngineBase {
     const size_t per = kRowLds;
     const int pb_max = this->pb_max();
     const int spread = level_slots((size_t)pb_max * per + 16);
-    SegTable t0{};
-    t0.n = (int32_t)S.seg_cnt.size();
-    t0.pb = balanced_chunk(S.F, pb_max, spread);
-    for (int q = 0; q < t0.n; q++) {
-      t0.base[q] = S.seg_base[q];
-      t0.cnt[q] = S.seg_cnt[q];
-      t0.chunk0[q + 1] = t0.chunk0[q] + (S.seg_cnt[q] + t0.pb - 1) / t0.pb;
-    }
+    const SegTable t0 = frontier_segs(S, balanced_chunk(S.F, pb_max, spread));
     // every set starts zeroed: the levels after a stop leave theirs untouched, and read zeros
     if (!qctr_clean) DSL_HIP(hipMemsetAsync(qctr, 0, (size_t)(kQueue + 1) * kCtrSet, stream));
     qctr_clean = false;
-    const auto tq0 = std::chrono::steady_clock::now();
+    const auto tq0 = Clock::now();
     const size_t lds = (size_t)pb_max * per + 16;
     for (int j = 0; j < nq; j++) {
       unsigned char* set = qctr + (size_t)j * kCtrSet;
-      LevelArgs<P> a{};
-      a.cur = (j & 1) ? S.next : S.cur;
-      a.cur_fp = (j & 1) ? S.next_fp : S.cur_fp;
+      LevelArgs<P> a = level_args(S, j & 1, lev0 + j, false, W > 1);
       a.segs = t0;
       a.qprev = j ? reinterpret_cast<const LevelCounters*>(set - kCtrSet) : nullptr;
       a.qprev_seg = j ? reinterpret_cast<const unsigned long long*>(set - kCtrSet + kCtrSegOff) : nullptr;
@@ -691,29 +768,14 @@ struct BfsEngine : EngineBase {
       a.qroom = room;
       a.qroom_half = room_half;
       a.qspread = spread;
-      a.t0_rt = t0_rt;
-      a.budget_rt = level_budget(W > 1);
       a.PB = pb_max;
       a.depth = depth + 1 + j;
       a.incremental = depth + j > init_depth ? 1 : 0;
-      a.next = (j & 1) ? S.cur : S.next;
-      a.next_fp = (j & 1) ? S.cur_fp : S.next_fp;
-      a.next_parent = S.hpar[lev0 + j];
-      a.next_event = S.hev[lev0 + j];
       a.seg_ctr = reinterpret_cast<unsigned long long*>(set + kCtrSegOff);
       a.zero_next = reinterpret_cast<uint4*>(set + kCtrSet);
       a.nseg = nseg;
       a.segcap = q_segcap;
-      a.spill = S.spill;
-      a.spill_cap = S.spill_cap;
       a.ctr = reinterpret_cast<LevelCounters*>(set);
-      a.terms = S.terms;
-      a.term_cap = term_cap;
-      a.table = tbl;
-      a.table.slots = S.table;
-      a.W = W;
-      a.me = S.gid;
-      a.owner_filter = 0;
       if (j == 0) DSL_HIP(hipEventRecord(qev[0], stream));
       const int grid = spread;  // the resident workgroups (the kernel loops over the chunks)
       launch_level<false>(grid, lds, a);
@@ -723,7 +785,7 @@ struct BfsEngine : EngineBase {
     stats.expand_launches += nq;  // every dispatch, also those after the stop (they return at once)
     DSL_HIP(hipMemcpyAsync(hq, qctr, (size_t)nq * kCtrSet, hipMemcpyDeviceToHost, stream));
     DSL_TRY(hsync());
-    q_ms_total = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count();
+    q_ms_total = ms_since(tq0);
     // the levels that ran: up to the first whose counters stop the queue (the device's rule)
     *ran = nq;
     for (int j = 0; j + 1 < nq; j++) {
@@ -878,32 +940,16 @@ struct BfsEngine : EngineBase {
     for (uint64_t c : S.seg_cnt) F += c;
     const int PB = chunk_parents(F);
     const int slots = level_slots((size_t)pb_max() * kRowLds + 16);
-    LevelArgs<P> a{};
-    a.cur = S.cur;
-    a.cur_fp = S.cur_fp;
-    a.segs.n = (int32_t)S.seg_cnt.size();
-    a.segs.pb = PB;
-    for (int q = 0; q < a.segs.n; q++) {
-      a.segs.base[q] = S.seg_base[q];
-      a.segs.cnt[q] = S.seg_cnt[q];
-      a.segs.chunk0[q + 1] = a.segs.chunk0[q] + (S.seg_cnt[q] + PB - 1) / PB;
-    }
+    LevelArgs<P> a = level_args(S, false, 0, true);
+    a.segs = frontier_segs(S, PB);
     a.PB = PB;
     a.depth = succ_depth;
     a.incremental = incremental ? 1 : 0;
-    a.next = S.next;
-    a.next_fp = S.next_fp;
-    a.next_parent = S.hpar[0];
-    a.next_event = S.hev[0];
     a.seg_ctr = reinterpret_cast<unsigned long long*>(S.find_ctr + kCtrSegOff);
     a.zero_next = reinterpret_cast<uint4*>(S.find_ctr + kCtrSet);
     a.nseg = 1;
     a.segcap = 0;
     a.ctr = reinterpret_cast<LevelCounters*>(S.find_ctr);
-    a.terms = S.terms;
-    a.term_cap = 1;
-    a.W = W;
-    a.me = S.gid;
     a.find = 1;
     a.find_key = key;
     a.qspread = slots;
@@ -970,13 +1016,7 @@ struct BfsEngine : EngineBase {
     a.cur = S.cur;
     a.cur_fp = S.cur_fp;
     const int per = mat_per_max<P>();
-    a.segs.n = (int32_t)S.seg_cnt.size();
-    a.segs.pb = per;
-    for (int q = 0; q < a.segs.n; q++) {
-      a.segs.base[q] = S.seg_base[q];
-      a.segs.cnt[q] = S.seg_cnt[q];
-      a.segs.chunk0[q + 1] = a.segs.chunk0[q] + (S.seg_cnt[q] + per - 1) / per;
-    }
+    a.segs = frontier_segs(S, per);
     a.me = S.gid;
     a.W = W;
     a.owner_filter = owner_filter ? 1 : 0;
@@ -1132,7 +1172,7 @@ struct BfsEngine : EngineBase {
   // records that carry them), one round trip; per watch the record with the smallest (fingerprint
   // lo, parent, event) among those of the minimum hi -- the order of terminals(), (hi, lo) -- and the
   // chains of all of them through the history arena (walk_chains). wit[w] gets the raw event
-  // indices; run_once replays them when the search ends.
+  // indices; build_result replays them when the search ends.
   struct WitnessTrace {
     int32_t depth = -1;
     std::vector<uint32_t> events;
@@ -1149,13 +1189,7 @@ struct BfsEngine : EngineBase {
     a.cur = S.cur;
     a.cur_fp = S.cur_fp;
     const int per = mat_per_max<P>();
-    a.segs.n = (int32_t)S.seg_cnt.size();
-    a.segs.pb = per;
-    for (int q = 0; q < a.segs.n; q++) {
-      a.segs.base[q] = S.seg_base[q];
-      a.segs.cnt[q] = S.seg_cnt[q];
-      a.segs.chunk0[q + 1] = a.segs.chunk0[q] + (S.seg_cnt[q] + per - 1) / per;
-    }
+    a.segs = frontier_segs(S, per);
     a.incremental = incremental ? 1 : 0;
     a.want = want;
     a.best = best;
@@ -1691,7 +1725,7 @@ struct BfsEngine : EngineBase {
   // terminal successors, and every state of the maxDepth level, are never written as rows, so there
   // is no device result to compare them with (the reference checks every non-terminal state before
   // its prune test, Search.java:201-220); the handlers that produce them are the same code. A
-  // multi-rank search sums the counts over the ranks (allreduce at the end of run_once).
+  // multi-rank search sums the counts over the ranks (allreduce in build_result).
   uint64_t chk_run = 0, chk_nd = 0, chk_ni = 0;
   dsl_event chk_first_nd{}, chk_first_ni{};
   // equal packed states: the header words and the records below the count (a device row's slots
@@ -1802,29 +1836,81 @@ struct BfsEngine : EngineBase {
     }
   }
 
-  int run_once(dsl_result** out) {
-    const auto t_start = t_run0;
+  // ---- one attempt, step by step ---------------------------------------------------------------
+  // SearchRun holds what lives as long as the attempt, LevelPlan what is decided before a level's
+  // kernels are launched, LevelOutcome what comes back from them; the member functions below are
+  // the steps of run_once, in the order it calls them.
+  struct FrontierTotals {  // a level's frontier over all shards (global_sum's words, in this order)
+    uint64_t states = 0, time_up = 0, work = 0;
+  };
+  struct LevelTotals {  // a level's counts over all shards (global_sum's words, in this order)
+    uint64_t new_states = 0, rows = 0, successors = 0, err_overflow = 0, err_table = 0, err_frontier = 0;
+    uint64_t work = 0, parents = 0;
+  };
+  struct SearchRun {
+    bool use_queue = false, trace_levels = false;
+    bool over = false;  // a step ended the search: the level loop stops
+    int n_watch = 0;
+    uint64_t init_enc = ~0ull;
+    uint64_t prev_new = 0, prev_work = 0;  // the last level's new states and work items (est_new_states)
+    // the last level's frontier growth (next frontier / frontier, all shards): the next frontier's
+    // rows are reserved for 1.25x that growth (at least 4x), so a protocol that grows faster than
+    // 4 new states per parent (the synthetic C3: ~5) does not spill every large level
+    uint64_t prev_front = 1;
+    double front_growth = 0;
+    bool rep_active = false, first_sharded = false;
+    // the watches' census of this attempt (a restarted search counts from zero): index i lines up
+    // with per_depth[i]
+    std::vector<std::vector<uint64_t>> census;
+    std::vector<uint64_t> census_total;
+    std::vector<WitnessTrace> wit;  // the witnesses of this attempt (a restarted search finds them again)
+    // a sharded level's gathered records already hold the next level's global frontier size, work
+    // and time-up flag (LevelPlan::g): no collective at the top of that next level
+    bool have_g = false;
+    FrontierTotals g_next;
+    std::vector<uint64_t> per_depth{1};
+    uint64_t total_states = 1, successors = 0, exchanged = 0, max_front = 1, x_levels = 0;
+    double x_sum_us = 0, level_ms_max = 0;
+    int end = DSL_SPACE_EXHAUSTED, pred_index = -1, term_depth = -1, depth = 0;
+  };
+  struct LevelPlan {
+    Clock::time_point lt0;
+    uint64_t reallocs0 = 0, exchanged0 = 0;
+    bool rep = false, route = false, queued = false, last_level = false;
+    bool owner_filter = false;  // the first sharded level expands only the parents each shard owns
+    FrontierTotals g;
+    int PB = 0, lslots = 0;
+    uint64_t slab = 0;  // records per sub-slab (LevelArgs::route_cs)
+    size_t lds = 0;
+  };
+  struct LevelOutcome {
+    std::vector<std::vector<unsigned long long>> segc;
+    std::vector<std::vector<uint64_t>> nbase, ncnt;
+    std::vector<uint64_t> span, recs;  // recs, sharded: W records of kRecWords (k_level_record), every rank's
+    float kms = 0;
+    LevelTotals sum;
+    uint64_t enc = ~0ull;
+    std::vector<TerminalRec> local_best;
+    uint64_t max_new = 0;    // the most states one shard's table took this level
+    bool level_tup = false;  // the level stopped at the deadline: partial
+    explicit LevelOutcome(size_t L)
+        : segc(L, std::vector<unsigned long long>(kSegs * kSegStride)), nbase(L), ncnt(L), span(L), local_best(L) {}
+  };
+
+  // Step: the buffers, the first table and the attempt's switches, before anything is enqueued.
+  int prepare_search(SearchRun& r) {
     if (comm_failed) {
       set_error("the engine's communicator was aborted by an earlier failure: create a new engine");
       return DSL_ERR_COMM;
     }
     (void)hipGetLastError();  // the per-thread sticky error must not blame this search for an older call
-    if (!stream) {
-      if (cfg.device >= 0) DSL_HIP(hipSetDevice(cfg.device));
-      DSL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      DSL_HIP(hipEventCreate(&ev0));
-      DSL_HIP(hipEventCreate(&ev1));
-    }
+    DSL_TRY(ensure_stream());
     stats = dsl_stats{};
     stats.state_bytes = NW * 4;
     stats.world_size = W;
     term_list.clear();
     term_total = 0;
-    if (!have_init) {
-      uint8_t tmp[sizeof(init)];
-      DSL_TRY(get_initial(tmp, sizeof(init)));
-    }
-    const int L = (int)sh.size();
+    DSL_TRY(ensure_init());
     // DSL_TERM_CAP (tests): TerminalRec entries per shard; 0 records none, so every terminal level
     // is resolved by the find-mode re-run
     const char* tc = getenv("DSL_TERM_CAP");
@@ -1841,7 +1927,7 @@ struct BfsEngine : EngineBase {
         DSL_HIP(hipMalloc(&S.table, buckets * 64));
         S.table_clean = false;
       }
-      // the table, counter sets and route counters are zeroed by k_setup (below)
+      // the table, counter sets and route counters are zeroed by k_setup (seed_search)
       if (!S.ctrbuf) DSL_HIP(hipMalloc(&S.ctrbuf, 2 * kCtrSet));
       if (!S.hctr) DSL_HIP(hipHostMalloc(&S.hctr, kCtrSet + sizeof(RouteCounters)));
       S.cset = 0;
@@ -1861,13 +1947,7 @@ struct BfsEngine : EngineBase {
       DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, 1024, false, 0));
       // every search starts with the same buffer of each pair as `cur`: the two then take the
       // same roles level by level in every search, so a repeated search reallocates nothing
-      if (S.flip) {
-        std::swap(S.cur, S.next);
-        std::swap(S.cur_cap, S.next_cap);
-        std::swap(S.cur_fp, S.next_fp);
-        std::swap(S.curfp_cap, S.nextfp_cap);
-        S.flip = false;
-      }
+      if (S.flip) swap_frontier(S);
       DSL_TRY(hist_grow(S, 0, 1, 0));
       S.level_size.assign(1, 0);
       S.F = 0;
@@ -1880,77 +1960,73 @@ struct BfsEngine : EngineBase {
       if (!t0_rt) DSL_HIP(hipMalloc(&t0_rt, 8));
       hipLaunchKernelGGL(k_clock, dim3(1), dim3(64), 0, stream, t0_rt);
       DSL_HIP(hipGetLastError());
-      const double left = hset.max_time_ms -
-                          std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
+      const double left = hset.max_time_ms - ms_since(t_run0);
       budget_rt = (uint64_t)std::max(1.0, left * 1e5);  // s_memrealtime: 100 MHz
     }
     stats.table_slots = buckets * 8 * (uint64_t)W;
     q_left = 0;
     q_pos = 0;
     // do_checks reads every level's rows right after the level: no device-side queue of levels
-    const bool use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE;
+    r.use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE;
     chk_run = chk_nd = chk_ni = 0;
     chk_first_nd = chk_first_ni = dsl_event{};
     if (const char* qr = getenv("DSL_QUEUE_ROWS")) q_rows_forced = std::max<uint64_t>(kSegs, strtoull(qr, nullptr, 10) / kSegs * kSegs);
-    const bool trace_levels = getenv("DSL_LEVEL_TRACE") != nullptr;
+    r.trace_levels = getenv("DSL_LEVEL_TRACE") != nullptr;
     tbl = Table{nullptr, buckets - 1, 0, 0};
     tbl.load_first = probe_load_first(buckets);
     while ((2ull << tbl.b0) <= buckets) tbl.b0++;  // log2(buckets): the key layout of this search
     inserted = 1;
-    uint64_t prev_new = 0, prev_work = 0;  // the last level's new states and work items (est_new_states)
-    // the last level's frontier growth (next frontier / frontier, all shards): the next frontier's
-    // rows are reserved for 1.25x that growth (at least 4x), so a protocol that grows faster than
-    // 4 new states per parent (the synthetic C3: ~5) does not spill every large level
-    uint64_t prev_front = 1;
-    double front_growth = 0;
+    return DSL_OK;
+  }
 
+  // Step: the initial state judged on the host and seeded on its owner shard, one k_setup per
+  // shard, and the verdict and the cost model agreed by every rank.
+  int seed_search(SearchRun& r) {
     // Seed: the initial state lives on its owner shard (BFS.initSearch, Search.java:434-440).
     const Fp init_fp = full_fingerprint<P>(init.w);
     const int init_owner = owner_of(init_fp, W);
-    uint64_t init_enc = ~0ull;
     // Replicated small levels: while the frontier is below rep_threshold, every shard runs the
     // whole level itself (identical work, no exchange; each table then holds every state of
     // those levels, a superset of what it owns, so later owner probes stay exact). The first
     // level above the threshold expands only owned parents, and from there on the search is
     // hash-sharded. Per-level latency of a sharded level is ~3 exchange rounds, so sharding a
     // level pays only once it has enough work.
-    bool rep_active = W > 1 && rep_threshold() > 0;
+    r.rep_active = W > 1 && rep_threshold() > 0;
     max_rank_work = 0;
-    bool first_sharded = W > 1 && !rep_active;
+    r.first_sharded = W > 1 && !r.rep_active;
     // checkState of the initial state: the same judge, on the host (no round trip before the
     // first level); k_setup only inserts its fingerprint
     {
       int pi = -1;
       const NodeView v0{init.w, P::kNodeWords, -1, nullptr};
       const int v = judge_view<P>(v0, prm, dset, init_depth, &pi);
-      init_enc = ((uint64_t)v << 32) | (uint32_t)(pi + 1);
+      r.init_enc = ((uint64_t)v << 32) | (uint32_t)(pi + 1);
     }
-    // the watches' census of this attempt (a restarted search counts from zero): index i lines up
-    // with per_depth[i]; the start state's watches are evaluated here, with its verdict
-    const int n_watch = dset.n_watch;
-    std::vector<std::vector<uint64_t>> census(n_watch, std::vector<uint64_t>(1, 0));
-    std::vector<uint64_t> census_total(n_watch, 0);
+    // the start state's watches are evaluated here, with its verdict
+    const int n_watch = r.n_watch = dset.n_watch;
+    r.census.assign(n_watch, std::vector<uint64_t>(1, 0));
+    r.census_total.assign(n_watch, 0);
     if (n_watch) {
       const NodeView v0{init.w, P::kNodeWords, -1, nullptr};
       const uint32_t held = eval_watches<P>(v0, prm, dset);
-      for (int w = 0; w < n_watch; w++) census[w][0] = census_total[w] = (held >> w) & 1u;
+      for (int w = 0; w < n_watch; w++) r.census[w][0] = r.census_total[w] = (held >> w) & 1u;
     }
-    // the witnesses of this attempt (a restarted search finds them again): a watch that holds on
-    // the start state has it as its witness, with an empty trace; the others wait in watch_want
-    std::vector<WitnessTrace> wit(n_watch);
+    // a watch that holds on the start state has it as its witness, with an empty trace; the
+    // others wait in watch_want
+    r.wit.resize(n_watch);
     dset.watch_want = n_watch ? witness_mask : 0u;
     for (int w = 0; w < n_watch; w++)
-      if (((dset.watch_want >> w) & 1u) && census[w][0]) {
-        wit[w].depth = init_depth;
+      if (((dset.watch_want >> w) & 1u) && r.census[w][0]) {
+        r.wit[w].depth = init_depth;
         dset.watch_want &= ~(1u << w);
       }
     for (auto& S : sh) {
       // one k_setup per shard: zeroes its table and counters; seeds the initial state's owner (or
       // every shard while small levels are replicated)
-      const bool seed = S.gid == init_owner || rep_active;
+      const bool seed = S.gid == init_owner || r.rep_active;
       SetupArgs<P> sa{};
       sa.table = reinterpret_cast<uint4*>(S.table);
-      sa.n_table = buckets * 4;
+      sa.n_table = table_buckets * 4;
       sa.clean = S.table_clean ? 1 : 0;
       S.table_clean = false;
       sa.ctr = reinterpret_cast<uint4*>(S.ctrbuf);
@@ -1976,9 +2052,9 @@ struct BfsEngine : EngineBase {
       S.level_size[0] = 1;
     }
     if (comm) {  // the initial state's verdict and the cost model, agreed by every rank (one collective)
-      uint64_t v[3] = {init_enc, ~(uint64_t)(cost_c_ns * 1e6), ~(uint64_t)(cost_x_us * 1e3)};
+      uint64_t v[3] = {r.init_enc, ~(uint64_t)(cost_c_ns * 1e6), ~(uint64_t)(cost_x_us * 1e3)};
       DSL_TRY(comm->allreduce_u64(v, 3, true, stream));
-      init_enc = v[0];
+      r.init_enc = v[0];
       stats.cost_c_ns = (double)~v[1] / 1e6;
       stats.cost_x_us = (double)~v[2] / 1e3;
     } else {
@@ -1994,554 +2070,549 @@ struct BfsEngine : EngineBase {
       shard_work_min = W > 1 ? (uint64_t)std::min(w, 1.8e19) : ~0ull;
       stats.shard_work_min = W > 1 ? shard_work_min : 0;
     }
-    const int init_verdict = (int)(init_enc >> 32);
-    if (trace_levels)
-      fprintf(stderr, "[setup] %.4f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+    if (r.trace_levels) fprintf(stderr, "[setup] %.4f ms\n", ms_since(t_run0));
 
     if (W > 1 && !xdev) {
       DSL_HIP(hipMalloc(&xdev, kXWords * 8));
       DSL_HIP(hipHostMalloc(&xhost, kXWords * 8));
     }
     stats.rccl_version = comm ? comm->version() : 0;
-    // a sharded level's gathered records already hold the next level's global frontier size, work
-    // and time-up flag (g below): no collective at the top of that next level
-    bool have_g = false;
-    std::vector<uint64_t> g_next(3, 0);
-    std::vector<uint64_t> per_depth{1};
-    uint64_t total_states = 1, successors = 0, exchanged = 0, max_front = 1, x_levels = 0;
-    double x_sum_us = 0;
-    int end = DSL_SPACE_EXHAUSTED, pred_index = -1, term_depth = -1;
-    int depth = init_depth;
-    double level_ms_max = 0;
+    r.depth = init_depth;
     progress_states = 1;
-    progress_depth = depth;
-    if (init_verdict >= V_TERM_EXCEPTION) {
-      end = init_verdict == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED : DSL_GOAL_FOUND;
-      pred_index = (int)(init_enc & 0xffffffffu) - 1;
-      term_depth = init_depth;
+    progress_depth = r.depth;
+    return DSL_OK;
+  }
+
+  // Step: the level's mode and the frontier every rank agrees on (p.g); the deadline or an empty
+  // frontier ends the search.
+  int agree_frontier(SearchRun& r, LevelPlan& p) {
+    p.lt0 = Clock::now();
+    p.reallocs0 = n_reallocs + stats.table_rehashes;
+    p.exchanged0 = r.exchanged;
+    // every shard holds the same frontier in a replicated level: the decision is identical
+    p.rep = r.rep_active && level_replicated(sh[0].F, sh[0].work);
+    if (r.rep_active && !p.rep) {
+      r.rep_active = false;
+      r.first_sharded = true;
+    }
+    p.route = W > 1 && !p.rep;
+    p.owner_filter = p.route && r.first_sharded;
+    if (p.route) r.first_sharded = false;
+    if (p.rep) {
+      p.g.states = sh[0].F;
+      p.g.work = sh[0].work;
     } else {
-      while (true) {
-        const auto lt0 = std::chrono::steady_clock::now();
-        const uint64_t reallocs0 = n_reallocs + stats.table_rehashes, exchanged0 = exchanged;
-        // every shard holds the same frontier in a replicated level: the decision is identical
-        const bool rep = rep_active && level_replicated(sh[0].F, sh[0].work);
-        if (rep_active && !rep) {
-          rep_active = false;
-          first_sharded = true;
-        }
-        const bool route = W > 1 && !rep;
-        std::vector<uint64_t> g(3, 0);  // [frontier states, time-up flag, work items]
-        if (rep) {
-          g[0] = sh[0].F;
-          g[2] = sh[0].work;
-        } else {
-          for (auto& S : sh) g[0] += S.F, g[2] += S.work;
-        }
-        if (hset.max_time_ms > 0) {
-          const double el =
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-          if (el > hset.max_time_ms) g[1] = 1;
-        }
-        if (have_g) {
-          g = g_next;
-          have_g = false;
-        } else if (!rep || hset.max_time_ms > 0) {
-          DSL_TRY(global_sum(g));
-        }
-        if (g[1]) {
-          end = DSL_TIME_EXHAUSTED;
-          break;
-        }
-        if (g[0] == 0) break;
+      for (auto& S : sh) p.g.states += S.F, p.g.work += S.work;
+    }
+    if (hset.max_time_ms > 0 && ms_since(t_run0) > hset.max_time_ms) p.g.time_up = 1;
+    if (r.have_g) {
+      p.g = r.g_next;
+      r.have_g = false;
+    } else if (!p.rep || hset.max_time_ms > 0) {
+      DSL_TRY(global_sum(p.g));
+    }
+    if (p.g.time_up) r.end = DSL_TIME_EXHAUSTED;
+    r.over = p.g.time_up || p.g.states == 0;
+    return DSL_OK;
+  }
 
-        if (use_queue && q_left == 0 && L == 1 && (W == 1 || rep) && sh[0].F > 0 &&
-            sh[0].F <= queue_flimit(queue_span(sh[0].F)) && sh[0].work <= 8 * queue_span(sh[0].F)) {
-          int ran = 0;
-          const auto tq0 = std::chrono::steady_clock::now();
-          DSL_TRY(ensure_table(inserted + est_new_states(sh[0].work, prev_new, prev_work)));
-          DSL_TRY(enqueue_queue(depth, std::chrono::duration<double, std::milli>(tq0 - t_start).count(), &ran));
-          if (trace_levels)
-            fprintf(stderr, "[queue] enqueue+run %.4f ms (loop entry %.4f ms after start)\n",
-                    std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tq0).count(),
-                    std::chrono::duration<double, std::milli>(tq0 - t_start).count());
-          q_left = ran;
-          q_pos = 0;
-        }
-        const bool queued = q_left > 0;
-        if (!queued) {
-          // a sharded level inserts about 1/W of its new states into each shard's table (+25 % for
-          // the hash's imbalance); a replicated or single-shard level all of them
-          const uint64_t est = est_new_states(g[2], prev_new, prev_work);
-          DSL_TRY(ensure_table(inserted + (route ? est / W + est / (4 * W) + 1024 : est)));
-        }
+  // Step: while the frontier is small and no queue is running, the next levels are enqueued back to
+  // back (enqueue_queue); p.queued says whether this level's counters come from a queue.
+  int start_queue(SearchRun& r, LevelPlan& p) {
+    const Shard& S = sh[0];
+    if (r.use_queue && q_left == 0 && sh.size() == 1 && (W == 1 || p.rep) && S.F > 0 &&
+        S.F <= queue_flimit(queue_span(S.F)) && S.work <= 8 * queue_span(S.F)) {
+      int ran = 0;
+      const auto tq0 = Clock::now();
+      const double entry_ms = std::chrono::duration<double, std::milli>(tq0 - t_run0).count();
+      DSL_TRY(ensure_table(inserted + est_new_states(S.work, r.prev_new, r.prev_work)));
+      DSL_TRY(enqueue_queue(r.depth, entry_ms, &ran));
+      if (r.trace_levels)
+        fprintf(stderr, "[queue] enqueue+run %.4f ms (loop entry %.4f ms after start)\n", ms_since(tq0), entry_ms);
+      q_left = ran;
+      q_pos = 0;
+    }
+    p.queued = q_left > 0;
+    return DSL_OK;
+  }
 
-        // Capacity: the level has exactly S.work work items, an upper bound on its new states.
-        // The next frontier gets min(work, 4F) rows (typical growth is ~3 new states per
-        // parent) split into nseg equal segments; VALID states beyond a segment's rows are
-        // spilled as 8-byte items (room for all `work` of them) and materialized after the
-        // kernel, so the estimate never fails and never reserves the worst case.
-        uint64_t Fmax = 0;
-        for (auto& S : sh) Fmax = std::max(Fmax, S.F);
-        const int PB = chunk_parents(Fmax, route);
-        // a sharded level: the slab (records per source -> owner pair the fast path moves without
-        // the host reading any count), from the global work and the last measured routed fraction;
-        // identical on every rank (its inputs are). The maxDepth level expands nothing further.
-        const bool last_level = hset.max_depth >= 0 && depth + 1 >= hset.max_depth;
-        uint64_t slab = 0;  // records per sub-slab (LevelArgs::route_cs)
-        if (route && slab_mode) {
-          // the most work one rank has: from the last sharded level's records; after replicated
-          // levels every rank expands the parents it owns (hash-balanced, g/W); a search sharded
-          // from its first level starts on the initial state's owner alone
-          const double per_rank = max_rank_work ? (double)max_rank_work
-                                  : rep_threshold() > 0 ? (double)g[2] / W : (double)g[2];
-          const double frac = route_frac > 0 ? route_frac : 1.0;
-          // 1.15x the expected records per sub-slab + one wave's 64: every sub-slab takes records of
-          // all four wave indexes of many workgroups (k_level), so the fill is even (1.3x before
-          // round 6, when a sub-slab took one wave index's records)
-          slab = (uint64_t)(1.15 * frac * per_rank / ((double)W * kRouteSegs)) + 64;
-          if (const char* m = getenv("DSL_SLAB_MAX")) slab = std::min<uint64_t>(slab, std::max(1, atoi(m)));  // tests
-        }
-        const int lslots = level_slots((size_t)pb_max() * kRowLds + 16, route);
-        if (queued) {
-          sh[0].nseg = kSegs;
-          sh[0].segcap = q_segcap;
-        } else {
-        for (auto& S : sh) {
-          S.ctr = reinterpret_cast<LevelCounters*>(S.ctrbuf + S.cset * kCtrSet);
-          S.seg_ctr = reinterpret_cast<unsigned long long*>(S.ctrbuf + S.cset * kCtrSet + kCtrSegOff);
-          // a shard that launches no k_level this level zeroes its next set here
-          if (S.F == 0) DSL_HIP(hipMemsetAsync(S.ctrbuf + (S.cset ^ 1) * kCtrSet, 0, kCtrSet, stream));
-          if (route) {  // every successor is routed: the rows come from k_materialize only
-            DSL_TRY(sharded_capacity(S, slab, last_level));
-            continue;
-          }
-          uint64_t nchunks = 0;
-          for (size_t q = 0; q < S.seg_cnt.size(); q++) nchunks += (S.seg_cnt[q] + PB - 1) / PB;
-          const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(nchunks, (uint64_t)lslots));
-          S.nseg = (int)std::min<uint64_t>(kSegs, blocks);
-          const uint64_t grown = (uint64_t)(1.25 * front_growth * (double)S.F);
-          const uint64_t want = std::min<uint64_t>(S.work, std::max<uint64_t>(std::max<uint64_t>(4 * S.F, grown), 8192)) + 1;
-          S.segcap = (want + S.nseg - 1) / S.nseg + 1;
-          const uint64_t rows = S.segcap * S.nseg;
-          DSL_TRY(grow_rows(&S.next, &S.next_cap, rows, false, 0));
-          DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, rows, false, 0));
-          DSL_TRY(hist_grow(S, S.level_size.size(), rows, 0));
-          DSL_TRY(grow(&S.spill, &S.spill_cap, std::max<uint64_t>(S.work, 1), false, 0));
-        }
-        }  // !queued (capacity)
-        const size_t lds = (size_t)PB * kRowLds + 16;
-        if (!queued) {
-        DSL_HIP(hipEventRecord(ev0, stream));
-        for (auto& S : sh) {
-          if (S.F == 0) continue;
-          LevelArgs<P> a{};
-          a.cur = S.cur;
-          a.cur_fp = S.cur_fp;
-          a.segs.n = (int32_t)S.seg_cnt.size();
-          a.segs.chunk0[0] = 0;
-          for (int q = 0; q < a.segs.n; q++) {
-            a.segs.base[q] = S.seg_base[q];
-            a.segs.cnt[q] = S.seg_cnt[q];
-            a.segs.chunk0[q + 1] = a.segs.chunk0[q] + (S.seg_cnt[q] + PB - 1) / PB;
-          }
-          a.PB = PB;
-          a.depth = depth + 1;
-          a.incremental = depth > init_depth ? 1 : 0;
-          a.next = S.next;
-          a.next_fp = S.next_fp;
-          a.next_parent = S.hpar[S.level_size.size()];
-          a.next_event = S.hev[S.level_size.size()];
-          a.seg_ctr = S.seg_ctr;
-          a.zero_next = reinterpret_cast<uint4*>(S.ctrbuf + (S.cset ^ 1) * kCtrSet);
-          a.nseg = S.nseg;
-          a.segcap = S.segcap;
-          a.spill = S.spill;
-          a.spill_cap = S.spill_cap;
-          a.ctr = S.ctr;
-          a.terms = S.terms;
-          a.term_cap = term_cap;
-          a.table = tbl;
-          a.table.slots = S.table;
-          a.W = W;
-          a.me = S.gid;
-          a.owner_filter = route && first_sharded ? 1 : 0;
-          a.out_key = S.out_key;
-          a.out_pk = slab ? S.out_pk : nullptr;
-          a.cap_pk = S.cap_pk;
-          a.out_item = S.out_item;
-          a.cap_fp = S.cap_fp;
-          a.route_cs = S.route_cs;
-          a.rc = S.rc;
-          a.rspill = S.rspill;
-          a.rspill_cap = S.rspill_cap;
-          a.judge_routed = route && last_level ? 1 : 0;
-          a.qprev = nullptr;
-          a.qprev_seg = nullptr;
-          a.segs.pb = PB;
-          a.qspread = lslots;
-          a.t0_rt = t0_rt;
-          a.budget_rt = level_budget(rep);
-          const uint64_t nchunks = a.segs.chunk0[a.segs.n];
-          const int blocks = (int)std::min<uint64_t>(nchunks, (uint64_t)lslots);
-          if (route)
-            launch_level<true>(blocks, lds, a);
-          else
-            launch_level<false>(blocks, lds, a);
-          DSL_HIP(hipGetLastError());
-        }
-        DSL_HIP(hipEventRecord(ev1, stream));
-        }  // !queued (launch)
-        // The level's counters. A sharded level runs its exchange first (sharded_fast): the
-        // owners' probes, the materialization and every shard's level record, then ONE host round
-        // trip; a single-shard or replicated level reads its counters right after k_level.
-        std::vector<std::vector<unsigned long long>> segc(L, std::vector<unsigned long long>(kSegs * kSegStride));
-        std::vector<std::vector<uint64_t>> nbase(L), ncnt(L);
-        std::vector<uint64_t> span(L);
-        std::vector<uint64_t> recs;  // sharded: W records of kRecWords (k_level_record), every rank's
-        const auto tx0 = std::chrono::steady_clock::now();
-        if (route) {
-          stats.sharded_levels++;
-          uint64_t time_up = 0;
-          if (hset.max_time_ms > 0 &&
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count() >
-                  hset.max_time_ms)
-            time_up = 1;
-          DSL_TRY(sharded_fast(depth, last_level, slab, time_up, recs, nbase, ncnt, span));
-          // the routed fraction of this level (all shards), for the next level's slab
-          uint64_t routed = 0, lw = 0;
-          for (int x = 0; x < W; x++) {
-            const uint64_t* r = recs.data() + (size_t)x * kRecWords;
-            lw += r[kRecWork];
-            for (int d = 0; d < W; d++) routed += r[kRecRoute + d];  // its own shard's included
-          }
-          if (lw) route_frac = std::max(0.05, (double)routed / (double)lw);
-          max_rank_work = 0;
-          for (int x = 0; x < W; x++) max_rank_work = std::max<uint64_t>(max_rank_work, recs[(size_t)x * kRecWords + kRecNextWork]);
-          for (int l = 0; l < L; l++)
-            for (int d = 0; d < W; d++)
-              if (d != sh[l].gid) exchanged += recs[(size_t)sh[l].gid * kRecWords + kRecRoute + d];
-        } else {
-        if (queued) {  // this level's counters came back with the queue
-          const unsigned char* set = hq + (size_t)q_pos * kCtrSet;
-          std::memcpy(&sh[0].lc, set, sizeof(LevelCounters));
-          // only the segments' counter words (one per 128-byte line) from the pinned host buffer
-          for (int q = 0; q < kSegs; q++)
-            std::memcpy(&segc[0][(size_t)q * kSegStride], set + kCtrSegOff + (size_t)q * kSegStride * 8, 8);
-        } else {
-          for (int l = 0; l < L; l++) {
-            Shard& S = sh[l];
-            DSL_HIP(hipMemcpyAsync(S.hctr, S.ctrbuf + S.cset * kCtrSet, kCtrSegOff + 8 * S.nseg * kSegStride,
-                                   hipMemcpyDeviceToHost, stream));
-          }
-          DSL_TRY(hsync());
-          for (int l = 0; l < L; l++) {
-            Shard& S = sh[l];
-            std::memcpy(&S.lc, S.hctr, sizeof(LevelCounters));
-            std::memcpy(segc[l].data(), S.hctr + kCtrSegOff, 8 * S.nseg * kSegStride);
-          }
-        }
-        // next frontier: the filled part of each segment, then the spill range
-        bool unspilled = false;
+  // Step: the table's room, the chunking and (sharded) the slab of this level, and the rows its
+  // next frontier may take.
+  int reserve_capacity(SearchRun& r, LevelPlan& p) {
+    if (!p.queued) {
+      // a sharded level inserts about 1/W of its new states into each shard's table (+25 % for
+      // the hash's imbalance); a replicated or single-shard level all of them
+      const uint64_t est = est_new_states(p.g.work, r.prev_new, r.prev_work);
+      DSL_TRY(ensure_table(inserted + (p.route ? est / W + est / (4 * W) + 1024 : est)));
+    }
+    // Capacity: the level has exactly S.work work items, an upper bound on its new states.
+    // The next frontier gets min(work, 4F) rows (typical growth is ~3 new states per
+    // parent) split into nseg equal segments; VALID states beyond a segment's rows are
+    // spilled as 8-byte items (room for all `work` of them) and materialized after the
+    // kernel, so the estimate never fails and never reserves the worst case.
+    uint64_t Fmax = 0;
+    for (auto& S : sh) Fmax = std::max(Fmax, S.F);
+    p.PB = chunk_parents(Fmax, p.route);
+    p.lds = (size_t)p.PB * kRowLds + 16;
+    // a sharded level: the slab (records per source -> owner pair the fast path moves without
+    // the host reading any count), from the global work and the last measured routed fraction;
+    // identical on every rank (its inputs are). The maxDepth level expands nothing further.
+    p.last_level = hset.max_depth >= 0 && r.depth + 1 >= hset.max_depth;
+    if (p.route && slab_mode) {
+      // the most work one rank has: from the last sharded level's records; after replicated
+      // levels every rank expands the parents it owns (hash-balanced, g/W); a search sharded
+      // from its first level starts on the initial state's owner alone
+      const double per_rank = max_rank_work ? (double)max_rank_work
+                              : rep_threshold() > 0 ? (double)p.g.work / W : (double)p.g.work;
+      const double frac = route_frac > 0 ? route_frac : 1.0;
+      // 1.15x the expected records per sub-slab + one wave's 64: every sub-slab takes records of
+      // all four wave indexes of many workgroups (k_level), so the fill is even (1.3x before
+      // round 6, when a sub-slab took one wave index's records)
+      p.slab = (uint64_t)(1.15 * frac * per_rank / ((double)W * kRouteSegs)) + 64;
+      if (const char* m = getenv("DSL_SLAB_MAX")) p.slab = std::min<uint64_t>(p.slab, std::max(1, atoi(m)));  // tests
+    }
+    p.lslots = level_slots((size_t)pb_max() * kRowLds + 16, p.route);
+    if (p.queued) {
+      sh[0].nseg = kSegs;
+      sh[0].segcap = q_segcap;
+      return DSL_OK;
+    }
+    for (auto& S : sh) {
+      S.ctr = reinterpret_cast<LevelCounters*>(S.ctrbuf + S.cset * kCtrSet);
+      S.seg_ctr = reinterpret_cast<unsigned long long*>(S.ctrbuf + S.cset * kCtrSet + kCtrSegOff);
+      // a shard that launches no k_level this level zeroes its next set here
+      if (S.F == 0) DSL_HIP(hipMemsetAsync(S.ctrbuf + (S.cset ^ 1) * kCtrSet, 0, kCtrSet, stream));
+      if (p.route) {  // every successor is routed: the rows come from k_materialize only
+        DSL_TRY(sharded_capacity(S, p.slab, p.last_level));
+        continue;
+      }
+      uint64_t nchunks = 0;
+      for (size_t q = 0; q < S.seg_cnt.size(); q++) nchunks += (S.seg_cnt[q] + p.PB - 1) / p.PB;
+      const uint64_t blocks = std::max<uint64_t>(1, std::min<uint64_t>(nchunks, (uint64_t)p.lslots));
+      S.nseg = (int)std::min<uint64_t>(kSegs, blocks);
+      const uint64_t grown = (uint64_t)(1.25 * r.front_growth * (double)S.F);
+      const uint64_t want = std::min<uint64_t>(S.work, std::max<uint64_t>(std::max<uint64_t>(4 * S.F, grown), 8192)) + 1;
+      S.segcap = (want + S.nseg - 1) / S.nseg + 1;
+      const uint64_t rows = S.segcap * S.nseg;
+      DSL_TRY(grow_rows(&S.next, &S.next_cap, rows, false, 0));
+      DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, rows, false, 0));
+      DSL_TRY(hist_grow(S, S.level_size.size(), rows, 0));
+      DSL_TRY(grow(&S.spill, &S.spill_cap, std::max<uint64_t>(S.work, 1), false, 0));
+    }
+    return DSL_OK;
+  }
+
+  // Step: one k_level per shard with a frontier, bracketed by the timing events (a queued level
+  // was launched with its queue).
+  int launch_levels(const SearchRun& r, const LevelPlan& p) {
+    if (p.queued) return DSL_OK;
+    DSL_HIP(hipEventRecord(ev0, stream));
+    for (auto& S : sh) {
+      if (S.F == 0) continue;
+      LevelArgs<P> a = level_args(S, false, S.level_size.size(), false, p.rep);
+      a.segs = frontier_segs(S, p.PB);
+      a.PB = p.PB;
+      a.depth = r.depth + 1;
+      a.incremental = r.depth > init_depth ? 1 : 0;
+      a.seg_ctr = S.seg_ctr;
+      a.zero_next = reinterpret_cast<uint4*>(S.ctrbuf + (S.cset ^ 1) * kCtrSet);
+      a.nseg = S.nseg;
+      a.segcap = S.segcap;
+      a.ctr = S.ctr;
+      a.owner_filter = p.owner_filter ? 1 : 0;
+      a.out_key = S.out_key;
+      a.out_pk = p.slab ? S.out_pk : nullptr;
+      a.cap_pk = S.cap_pk;
+      a.out_item = S.out_item;
+      a.cap_fp = S.cap_fp;
+      a.route_cs = S.route_cs;
+      a.rc = S.rc;
+      a.rspill = S.rspill;
+      a.rspill_cap = S.rspill_cap;
+      a.judge_routed = p.route && p.last_level ? 1 : 0;
+      a.qspread = p.lslots;
+      const uint64_t nchunks = a.segs.chunk0[a.segs.n];
+      const int blocks = (int)std::min<uint64_t>(nchunks, (uint64_t)p.lslots);
+      if (p.route)
+        launch_level<true>(blocks, p.lds, a);
+      else
+        launch_level<false>(blocks, p.lds, a);
+      DSL_HIP(hipGetLastError());
+    }
+    DSL_HIP(hipEventRecord(ev1, stream));
+    return DSL_OK;
+  }
+
+  // Step: the level's counters and its next frontier's row ranges (o.nbase / o.ncnt / o.span). A
+  // sharded level runs its exchange first (sharded_fast): the owners' probes, the materialization
+  // and every shard's level record, then ONE host round trip; a single-shard or replicated level
+  // reads its counters right after k_level, a queued one has them already.
+  int read_counters(SearchRun& r, const LevelPlan& p, LevelOutcome& o) {
+    const int L = (int)sh.size();
+    const auto tx0 = Clock::now();
+    if (p.route) {
+      stats.sharded_levels++;
+      const uint64_t time_up = hset.max_time_ms > 0 && ms_since(t_run0) > hset.max_time_ms ? 1 : 0;
+      DSL_TRY(sharded_fast(r.depth, p.last_level, p.slab, time_up, o.recs, o.nbase, o.ncnt, o.span));
+      // the routed fraction of this level (all shards), for the next level's slab
+      uint64_t routed = 0, lw = 0;
+      for (int x = 0; x < W; x++) {
+        const uint64_t* rec = o.recs.data() + (size_t)x * kRecWords;
+        lw += rec[kRecWork];
+        for (int d = 0; d < W; d++) routed += rec[kRecRoute + d];  // its own shard's included
+      }
+      if (lw) route_frac = std::max(0.05, (double)routed / (double)lw);
+      max_rank_work = 0;
+      for (int x = 0; x < W; x++) max_rank_work = std::max<uint64_t>(max_rank_work, o.recs[(size_t)x * kRecWords + kRecNextWork]);
+      for (int l = 0; l < L; l++)
+        for (int d = 0; d < W; d++)
+          if (d != sh[l].gid) r.exchanged += o.recs[(size_t)sh[l].gid * kRecWords + kRecRoute + d];
+      // the exchange rounds, the owners' probes and the materialization, up to the counters
+      stats.exchange_ms += ms_since(tx0);
+    } else {
+      if (p.queued) {  // this level's counters came back with the queue
+        const unsigned char* set = hq + (size_t)q_pos * kCtrSet;
+        std::memcpy(&sh[0].lc, set, sizeof(LevelCounters));
+        // only the segments' counter words (one per 128-byte line) from the pinned host buffer
+        for (int q = 0; q < kSegs; q++)
+          std::memcpy(&o.segc[0][(size_t)q * kSegStride], set + kCtrSegOff + (size_t)q * kSegStride * 8, 8);
+      } else {
+        for (auto& S : sh)
+          DSL_HIP(hipMemcpyAsync(S.hctr, S.ctrbuf + S.cset * kCtrSet, kCtrSegOff + 8 * S.nseg * kSegStride,
+                                 hipMemcpyDeviceToHost, stream));
+        DSL_TRY(hsync());
         for (int l = 0; l < L; l++) {
           Shard& S = sh[l];
-          for (int q = 0; q < S.nseg; q++) {
-            const uint64_t c = std::min<uint64_t>(segc[l][(size_t)q * kSegStride], S.segcap);
-            if (c) {
-              nbase[l].push_back((uint64_t)q * S.segcap);
-              ncnt[l].push_back(c);
-            }
-          }
-          span[l] = S.segcap * S.nseg;
-          const uint64_t ns = std::min<uint64_t>(S.lc.spilled, S.spill_cap);
-          if (!ns || S.lc.err_frontier || S.lc.err_overflow) continue;
-          unspilled = true;
-          const uint64_t keep = span[l], need = keep + ns;
-          const size_t lv = S.level_size.size();
-          DSL_TRY(grow_rows(&S.next, &S.next_cap, need, true, keep));
-          DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, need, true, keep));
-          DSL_TRY(hist_grow(S, lv, need, keep));
-          const int blocks = (int)std::min<uint64_t>((ns + kBlock - 1) / kBlock, 256ull * 32);
-          LevelCounters* uctr = queued ? reinterpret_cast<LevelCounters*>(qctr + (size_t)q_pos * kCtrSet) : S.ctr;
-          hipLaunchKernelGGL(k_unspill<P>, dim3(blocks), dim3(kBlock), 0, stream, S.spill, ns, S.cur, S.cur_fp, S.next,
-                             S.next_fp, S.hpar[lv], S.hev[lv], keep, S.gid, uctr, prm, dset, nullptr);
-          nbase[l].push_back(keep);
-          ncnt[l].push_back(ns);
-          span[l] = need;
-        }
-        if (unspilled) {  // counters changed after the first read (next_work)
-          for (auto& S : sh) {
-            const void* src = queued ? (const void*)(qctr + (size_t)q_pos * kCtrSet) : (const void*)S.ctr;
-            DSL_HIP(hipMemcpyAsync(S.hctr, src, sizeof(LevelCounters), hipMemcpyDeviceToHost, stream));
-          }
-          DSL_TRY(hsync());
-          for (auto& S : sh) std::memcpy(&S.lc, S.hctr, sizeof(LevelCounters));
-        }
-        }  // !route
-        if (route)  // the exchange rounds, the owners' probes and the materialization, up to the counters
-          stats.exchange_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - tx0).count();
-        float kms = 0;
-        if (!queued || q_pos == 0) {  // a queue is timed as a whole (its dispatches counted there)
-          if (queued) kms = (float)q_ms_total;
-          else (void)hipEventElapsedTime(&kms, ev0, ev1);
-          stats.expand_ms += kms;
-        }
-        if (!queued) stats.expand_launches++;
-#ifdef DSL_PHASES
-        for (auto& S : sh) {
-          const auto& q = S.lc.phase;
-          fprintf(stderr, "[phases] depth %d F=%llu work=%llu new=%llu cycles:", depth + 1, (unsigned long long)S.F,
-                  (unsigned long long)S.lc.work_items, (unsigned long long)S.lc.new_states);
-          for (int i = 0; i < 12; i++) fprintf(stderr, " %.3g", (double)q[i]);
-          fprintf(stderr, "\n[phcls] depth %d", depth + 1);
-          for (int c = 0; c < 16; c++)
-            if (S.lc.phcls[16 + c])
-              fprintf(stderr, " c%d: %.3g cyc / %llu passes (%.0f)", c, (double)S.lc.phcls[c],
-                      (unsigned long long)S.lc.phcls[16 + c], (double)S.lc.phcls[c] / S.lc.phcls[16 + c]);
-          if (S.lc.phcls[31]) {  // k_materialize (sharded levels): cycles per wave pass by phase
-            fprintf(stderr, "\n[matph] depth %d passes %llu cycles/pass: items %.0f stage %.0f handler %.0f judge %.0f "
-                    "reserve+count %.0f emit %.0f", depth + 1, (unsigned long long)S.lc.phcls[31],
-                    (double)S.lc.phcls[10] / S.lc.phcls[31], (double)S.lc.phcls[11] / S.lc.phcls[31],
-                    (double)S.lc.phcls[12] / S.lc.phcls[31], (double)S.lc.phcls[13] / S.lc.phcls[31],
-                    (double)S.lc.phcls[14] / S.lc.phcls[31], (double)S.lc.phcls[15] / S.lc.phcls[31]);
-          }
-          fprintf(stderr, "\n");
-        }
-#elif defined(DSL_TIMELINE)
-        for (auto& S : sh) {
-          const auto& q = S.lc.phase;
-          const unsigned long long t0 = ~q[0];  // the earliest workgroup entry
-          fprintf(stderr, "[timeline] depth %d F=%llu work=%llu | all WGs %.2f us | WG0 entry +%.2f:", depth + 1,
-                  (unsigned long long)S.F, (unsigned long long)S.lc.work_items, (q[1] - t0) / 100.0,
-                  ((long long)q[2] - (long long)t0) / 100.0);
-          for (int i = 0; i < 32 && S.lc.phcls[i]; i++)
-            fprintf(stderr, " %llu@%.2f", S.lc.phcls[i] >> 56,
-                    ((long long)(S.lc.phcls[i] & ((1ull << 56) - 1)) - (long long)(t0 & ((1ull << 56) - 1))) / 100.0);
-          fprintf(stderr, "\n");
-        }
-#endif
-        // global counts, errors, terminal selection
-        std::vector<uint64_t> gsum(8, 0);
-        uint64_t enc = ~0ull;
-        std::vector<TerminalRec> local_best(L);
-        uint64_t max_new = 0;  // the most states one shard's table took this level
-        bool level_tup = false;  // the level stopped at the deadline: partial
-        for (int l = 0; l < (rep ? 1 : L); l++) {  // replicated: every shard has the same counts
-          Shard& S = sh[l];
-          gsum[0] += S.lc.new_states;
-          max_new = std::max<uint64_t>(max_new, S.lc.new_states);
-          level_tup |= S.lc.time_up != 0;
-          uint64_t fn = 0;
-          for (uint64_t c : ncnt[l]) fn += c;
-          gsum[1] += fn;
-          gsum[2] += S.lc.successors;
-          gsum[3] += S.lc.err_overflow;
-          gsum[4] += S.lc.err_table;
-          gsum[5] += S.lc.err_frontier;
-          gsum[6] += S.lc.work_items;
-          gsum[7] += S.F;
-          stats.parents += S.F;
-          stats.work_items += S.lc.work_items;
-          stats.new_states += S.lc.new_states;
-          stats.probes += S.lc.probes;
-          stats.appended += fn;
-          if (S.lc.term_best && recs.empty()) {  // the level's exact best terminal (fold_terminals)
-            const uint64_t key = ~(uint64_t)S.lc.term_best;
-            DSL_TRY(resolve_terminal(S, key, depth + 1, depth > init_depth, &local_best[l]));
-            enc = std::min<uint64_t>(enc, (key & ~(uint64_t)0xff) | (uint64_t)S.gid);
-          }
-        }
-        if (!recs.empty()) {  // the gathered records: global sums, the best terminal, the next level's g
-          std::fill(gsum.begin(), gsum.end(), 0);
-          std::fill(g_next.begin(), g_next.end(), 0);
-          max_new = 0;
-          for (int x = 0; x < W; x++) {
-            const uint64_t* r = recs.data() + (size_t)x * kRecWords;
-            gsum[0] += r[kRecNew];
-            max_new = std::max<uint64_t>(max_new, r[kRecNew]);
-            level_tup |= r[kRecLevelTimeUp] != 0;
-            gsum[1] += r[kRecRows];
-            gsum[2] += r[kRecSucc];
-            gsum[3] += r[kRecErrOverflow];
-            gsum[4] += r[kRecErrTable];
-            gsum[5] += r[kRecErrFrontier];
-            gsum[6] += r[kRecWork];
-            gsum[7] += r[kRecParents];
-            enc = std::min<uint64_t>(enc, r[kRecTerm]);
-            g_next[0] += r[kRecRows];
-            g_next[1] = std::max<uint64_t>(g_next[1], r[kRecTimeUp]);
-            g_next[2] += r[kRecNextWork];
-          }
-          have_g = true;
-          for (int l = 0; l < L; l++) {
-            Shard& S = sh[l];
-            if (enc != ~0ull && (int)(enc & 0xff) == S.gid)  // this shard holds the level's best terminal
-              DSL_TRY(resolve_terminal(S, ~(uint64_t)S.lc.term_best, depth + 1, depth > init_depth, &local_best[l]));
-          }
-        } else if (!rep) {
-          DSL_TRY(global_sum(gsum));
-          if (comm) {
-            stats.host_syncs++;
-            DSL_TRY(comm->allreduce_u64(&enc, 1, true, stream));
-          }
-        }
-        const bool owner_filtered = route && first_sharded;  // this level expanded only the parents each shard owns
-        if (route) first_sharded = false;
-        if (gsum[3]) {
-          set_error("a successor exceeded the packed state's bounds (" + std::to_string(gsum[3]) + " times)");
-          return DSL_ERR_STATE_OVERFLOW;
-        }
-        if (gsum[4]) {
-          set_error("visited table full: raise table_log2_slots");
-          return DSL_ERR_TABLE_FULL;
-        }
-        if (gsum[5]) {
-          set_error("next frontier exceeds capacity");
-          return DSL_ERR_FRONTIER_FULL;
-        }
-        if (hset.max_frontier_states > 0 && gsum[1] > hset.max_frontier_states) {
-          set_error("the frontier of depth " + std::to_string(depth + 1) + " holds " + std::to_string(gsum[1]) +
-                    " states, more than max_frontier_states");
-          return DSL_ERR_FRONTIER_FULL;
-        }
-        if (gsum[7]) avg_events_x16 = std::max<uint64_t>(16, (gsum[6] * 16 + gsum[7] - 1) / gsum[7]);
-        if (level_tup && enc == ~0ull) {
-          // the deadline passed inside the level (Search.java:313-318): its states count, but it is
-          // not a completed depth; a terminal it found is still reported (below)
-          successors += gsum[2];
-          total_states += gsum[0];
-          for (int w = 0; w < n_watch; w++) census_total[w] += sh[0].lc.watch[w];  // as `states`: not a completed level
-          progress_states = total_states;
-          end = DSL_TIME_EXHAUSTED;
-          break;
-        }
-        depth++;
-        successors += gsum[2];
-        total_states += gsum[0];
-        for (int w = 0; w < n_watch; w++) {  // a completed level (single levels and queued ones alike)
-          census_total[w] += sh[0].lc.watch[w];
-          if (gsum[0]) census[w].push_back(sh[0].lc.watch[w]);
-        }
-        inserted += route ? max_new : gsum[0];  // per shard (an upper bound)
-        prev_new = gsum[0];
-        prev_work = gsum[6];
-        if (gsum[1]) {  // the level's parents: gsum[7] when counted, else the last frontier
-          front_growth = (double)gsum[1] / (double)(gsum[7] ? gsum[7] : prev_front);
-          prev_front = gsum[1];
-        }
-        if (gsum[0]) per_depth.push_back(gsum[0]);
-        max_front = std::max(max_front, gsum[1]);
-        progress_states = total_states;
-        progress_depth = depth;
-        for (int l = 0; l < L; l++) {
-          Shard& S = sh[l];
-          S.level_size.push_back(span[l]);
-        }
-        // a wanted watch's first non-zero count in a completed level: its witness, while the level's
-        // parents are still in S.cur (a level the deadline cut short is not enumerated)
-        if (dset.watch_want && !level_tup && watch_wanted_hit(sh[0].lc, dset.watch_want)) {
-          uint32_t hit = 0;
-          for (int w = 0; w < n_watch; w++)
-            if (((dset.watch_want >> w) & 1u) && sh[0].lc.watch[w]) hit |= 1u << w;
-          DSL_TRY(find_witnesses(sh[0], hit, depth, depth - 1 > init_depth, wit));
-          dset.watch_want &= ~hit;  // later levels queue as before
-        }
-        const double lms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - lt0).count();
-        level_ms_max = std::max(level_ms_max, lms);
-        // the cost model (auto replicate_below): c from levels in the throughput regime, X from the
-        // sharded levels that allocated nothing (a first search grows its buffers)
-        if (!queued && kms > 0) {
-          uint64_t lw = 0;
-          for (auto& S : sh) lw += S.lc.work_items;
-          if (lw >= 65536) {
-            const double c = (double)kms * 1e6 / (double)lw;
-            cost_c_ns = cost_c_ns > 0 ? std::min(cost_c_ns, c) : c;
-          }
-          if (route && n_reallocs + stats.table_rehashes == reallocs0) {
-            x_sum_us += std::max(0.0, (lms - (double)kms) * 1000.0);
-            x_levels++;
-          }
-        }
-        if (trace_levels)
-          fprintf(stderr, "[level] depth %d F=%llu new=%llu queued=%d wall_ms=%.4f kernel_ms=%.4f sharded=%d "
-                  "routed=%llu reallocs=%llu\n", depth, (unsigned long long)gsum[7], (unsigned long long)gsum[0],
-                  queued ? 1 : 0, lms, (double)kms, route ? 1 : 0, (unsigned long long)(exchanged - exchanged0),
-                  (unsigned long long)n_reallocs);
-        if (enc != ~0ull) {
-          const int wrank = (int)(enc & 0xff);
-          uint64_t rec[4] = {0, 0, 0, 0};
-          for (int l = 0; l < L; l++)
-            if (sh[l].gid == wrank) {
-              const TerminalRec& b = local_best[l];
-              rec[0] = ((uint64_t)wrank << 48) | b.parent;
-              rec[1] = b.event;
-              rec[2] = (uint64_t)b.verdict;
-              rec[3] = (uint64_t)(b.pred_index + 1);
-            }
-          if (comm && !rep) DSL_TRY((stats.host_syncs++, comm->bcast_u64(rec, 4, wrank, stream)));
-          const int v = (int)rec[2];
-          end = v == V_TERM_EXCEPTION ? DSL_EXCEPTION_THROWN : v == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED
-                                                                                     : DSL_GOAL_FOUND;
-          pred_index = v == V_TERM_EXCEPTION ? -1 : (int)rec[3] - 1;
-          term_depth = depth;
-          // walk parent pointers back level by level (across shards)
-          std::vector<uint32_t> evs{(uint32_t)rec[1]};
-          uint64_t ref = rec[0];
-          const int nlev = (int)sh[0].level_size.size();
-          for (int lev = nlev - 2; lev >= 1; lev--) {
-            const int r = (int)(ref >> 48);
-            const uint64_t idx = ref & ((1ull << 48) - 1);
-            uint64_t hop[2] = {0, 0};
-            for (int l = 0; l < L; l++)
-              if (sh[l].gid == r) {
-                uint64_t p;
-                uint32_t e;
-                DSL_HIP(hipMemcpy(&p, sh[l].hpar[lev] + idx, 8, hipMemcpyDeviceToHost));
-                DSL_HIP(hipMemcpy(&e, sh[l].hev[lev] + idx, 4, hipMemcpyDeviceToHost));
-                hop[0] = p;
-                hop[1] = e;
-              }
-            // a terminal of a replicated level has a local chain on every rank: no exchange
-            if (comm && !rep) DSL_TRY((stats.host_syncs++, comm->bcast_u64(hop, 2, r, stream)));
-            evs.push_back((uint32_t)hop[1]);
-            ref = hop[0];
-          }
-          std::reverse(evs.begin(), evs.end());
-          trace_events = evs;
-          // every terminal of this level (a level the deadline cut short is not enumerated)
-          if (hset.max_terminals > 0 && !level_tup)
-            DSL_TRY(list_terminals(depth, depth - 1 > init_depth, rep, owner_filtered));
-          break;
-        }
-        if (hset.do_checks != DSL_CHECKS_NONE)
-          for (int l = 0; l < L; l++) DSL_TRY(run_checks(sh[l], nbase[l], ncnt[l]));
-        if (gsum[1] == 0) break;
-        for (int l = 0; l < L; l++) {
-          Shard& S = sh[l];
-          std::swap(S.cur, S.next);
-          std::swap(S.cur_cap, S.next_cap);
-          std::swap(S.cur_fp, S.next_fp);
-          std::swap(S.curfp_cap, S.nextfp_cap);
-          S.flip = !S.flip;
-          S.seg_base = nbase[l];
-          S.seg_cnt = ncnt[l];
-          S.F = 0;
-          for (uint64_t c : ncnt[l]) S.F += c;
-          S.work = S.lc.next_work;
-          if (!queued) S.cset ^= 1;  // queued levels used the queue's counter sets
-        }
-        if (queued) {
-          q_pos++;
-          q_left--;
+          std::memcpy(&S.lc, S.hctr, sizeof(LevelCounters));
+          std::memcpy(o.segc[l].data(), S.hctr + kCtrSegOff, 8 * S.nseg * kSegStride);
         }
       }
+      DSL_TRY(collect_rows(p, o));
     }
-    if (trace_levels)
-      fprintf(stderr, "[levels] %.4f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+    if (!p.queued || q_pos == 0) {  // a queue is timed as a whole (its dispatches counted there)
+      if (p.queued) o.kms = (float)q_ms_total;
+      else (void)hipEventElapsedTime(&o.kms, ev0, ev1);
+      stats.expand_ms += o.kms;
+    }
+    if (!p.queued) stats.expand_launches++;
+    print_phases(r.depth);
+    return DSL_OK;
+  }
+
+  // The next frontier of a level that routed nothing: the filled part of each segment, then the
+  // spill range (k_unspill materializes the spilled items behind the segments).
+  int collect_rows(const LevelPlan& p, LevelOutcome& o) {
+    bool unspilled = false;
+    for (size_t l = 0; l < sh.size(); l++) {
+      Shard& S = sh[l];
+      for (int q = 0; q < S.nseg; q++) {
+        const uint64_t c = std::min<uint64_t>(o.segc[l][(size_t)q * kSegStride], S.segcap);
+        if (c) {
+          o.nbase[l].push_back((uint64_t)q * S.segcap);
+          o.ncnt[l].push_back(c);
+        }
+      }
+      o.span[l] = S.segcap * S.nseg;
+      const uint64_t ns = std::min<uint64_t>(S.lc.spilled, S.spill_cap);
+      if (!ns || S.lc.err_frontier || S.lc.err_overflow) continue;
+      unspilled = true;
+      const uint64_t keep = o.span[l], need = keep + ns;
+      const size_t lv = S.level_size.size();
+      DSL_TRY(grow_rows(&S.next, &S.next_cap, need, true, keep));
+      DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, need, true, keep));
+      DSL_TRY(hist_grow(S, lv, need, keep));
+      const int blocks = (int)std::min<uint64_t>((ns + kBlock - 1) / kBlock, 256ull * 32);
+      LevelCounters* uctr = p.queued ? reinterpret_cast<LevelCounters*>(qctr + (size_t)q_pos * kCtrSet) : S.ctr;
+      hipLaunchKernelGGL(k_unspill<P>, dim3(blocks), dim3(kBlock), 0, stream, S.spill, ns, S.cur, S.cur_fp, S.next,
+                         S.next_fp, S.hpar[lv], S.hev[lv], keep, S.gid, uctr, prm, dset, nullptr);
+      o.nbase[l].push_back(keep);
+      o.ncnt[l].push_back(ns);
+      o.span[l] = need;
+    }
+    if (unspilled) {  // counters changed after the first read (next_work)
+      for (auto& S : sh) {
+        const void* src = p.queued ? (const void*)(qctr + (size_t)q_pos * kCtrSet) : (const void*)S.ctr;
+        DSL_HIP(hipMemcpyAsync(S.hctr, src, sizeof(LevelCounters), hipMemcpyDeviceToHost, stream));
+      }
+      DSL_TRY(hsync());
+      for (auto& S : sh) std::memcpy(&S.lc, S.hctr, sizeof(LevelCounters));
+    }
+    return DSL_OK;
+  }
+
+  // The instrumented builds' per-level lines (tools/build_variant.sh); nothing in the product.
+  void print_phases([[maybe_unused]] int depth) {
+#ifdef DSL_PHASES
+    for (auto& S : sh) {
+      const auto& q = S.lc.phase;
+      fprintf(stderr, "[phases] depth %d F=%llu work=%llu new=%llu cycles:", depth + 1, (unsigned long long)S.F,
+              (unsigned long long)S.lc.work_items, (unsigned long long)S.lc.new_states);
+      for (int i = 0; i < 12; i++) fprintf(stderr, " %.3g", (double)q[i]);
+      fprintf(stderr, "\n[phcls] depth %d", depth + 1);
+      for (int c = 0; c < 16; c++)
+        if (S.lc.phcls[16 + c])
+          fprintf(stderr, " c%d: %.3g cyc / %llu passes (%.0f)", c, (double)S.lc.phcls[c],
+                  (unsigned long long)S.lc.phcls[16 + c], (double)S.lc.phcls[c] / S.lc.phcls[16 + c]);
+      if (S.lc.phcls[31]) {  // k_materialize (sharded levels): cycles per wave pass by phase
+        fprintf(stderr, "\n[matph] depth %d passes %llu cycles/pass: items %.0f stage %.0f handler %.0f judge %.0f "
+                "reserve+count %.0f emit %.0f", depth + 1, (unsigned long long)S.lc.phcls[31],
+                (double)S.lc.phcls[10] / S.lc.phcls[31], (double)S.lc.phcls[11] / S.lc.phcls[31],
+                (double)S.lc.phcls[12] / S.lc.phcls[31], (double)S.lc.phcls[13] / S.lc.phcls[31],
+                (double)S.lc.phcls[14] / S.lc.phcls[31], (double)S.lc.phcls[15] / S.lc.phcls[31]);
+      }
+      fprintf(stderr, "\n");
+    }
+#elif defined(DSL_TIMELINE)
+    for (auto& S : sh) {
+      const auto& q = S.lc.phase;
+      const unsigned long long t0 = ~q[0];  // the earliest workgroup entry
+      fprintf(stderr, "[timeline] depth %d F=%llu work=%llu | all WGs %.2f us | WG0 entry +%.2f:", depth + 1,
+              (unsigned long long)S.F, (unsigned long long)S.lc.work_items, (q[1] - t0) / 100.0,
+              ((long long)q[2] - (long long)t0) / 100.0);
+      for (int i = 0; i < 32 && S.lc.phcls[i]; i++)
+        fprintf(stderr, " %llu@%.2f", S.lc.phcls[i] >> 56,
+                ((long long)(S.lc.phcls[i] & ((1ull << 56) - 1)) - (long long)(t0 & ((1ull << 56) - 1))) / 100.0);
+      fprintf(stderr, "\n");
+    }
+#endif
+  }
+
+  // Step: the level's totals over all shards (o.sum), its best terminal key (o.enc) and, on the
+  // shard that holds it, the terminal's record (o.local_best).
+  int fold_totals(SearchRun& r, const LevelPlan& p, LevelOutcome& o) {
+    const int L = (int)sh.size();
+    for (int l = 0; l < (p.rep ? 1 : L); l++) {  // replicated: every shard has the same counts
+      Shard& S = sh[l];
+      o.sum.new_states += S.lc.new_states;
+      o.max_new = std::max<uint64_t>(o.max_new, S.lc.new_states);
+      o.level_tup |= S.lc.time_up != 0;
+      uint64_t fn = 0;
+      for (uint64_t c : o.ncnt[l]) fn += c;
+      o.sum.rows += fn;
+      o.sum.successors += S.lc.successors;
+      o.sum.err_overflow += S.lc.err_overflow;
+      o.sum.err_table += S.lc.err_table;
+      o.sum.err_frontier += S.lc.err_frontier;
+      o.sum.work += S.lc.work_items;
+      o.sum.parents += S.F;
+      stats.parents += S.F;
+      stats.work_items += S.lc.work_items;
+      stats.new_states += S.lc.new_states;
+      stats.probes += S.lc.probes;
+      stats.appended += fn;
+      if (S.lc.term_best && o.recs.empty()) {  // the level's exact best terminal (fold_terminals)
+        const uint64_t key = ~(uint64_t)S.lc.term_best;
+        DSL_TRY(resolve_terminal(S, key, r.depth + 1, r.depth > init_depth, &o.local_best[l]));
+        o.enc = std::min<uint64_t>(o.enc, (key & ~(uint64_t)0xff) | (uint64_t)S.gid);
+      }
+    }
+    if (!o.recs.empty()) {  // the gathered records: global sums, the best terminal, the next level's g
+      o.sum = LevelTotals{};
+      r.g_next = FrontierTotals{};
+      o.max_new = 0;
+      for (int x = 0; x < W; x++) {
+        const uint64_t* rec = o.recs.data() + (size_t)x * kRecWords;
+        o.sum.new_states += rec[kRecNew];
+        o.max_new = std::max<uint64_t>(o.max_new, rec[kRecNew]);
+        o.level_tup |= rec[kRecLevelTimeUp] != 0;
+        o.sum.rows += rec[kRecRows];
+        o.sum.successors += rec[kRecSucc];
+        o.sum.err_overflow += rec[kRecErrOverflow];
+        o.sum.err_table += rec[kRecErrTable];
+        o.sum.err_frontier += rec[kRecErrFrontier];
+        o.sum.work += rec[kRecWork];
+        o.sum.parents += rec[kRecParents];
+        o.enc = std::min<uint64_t>(o.enc, rec[kRecTerm]);
+        r.g_next.states += rec[kRecRows];
+        r.g_next.time_up = std::max<uint64_t>(r.g_next.time_up, rec[kRecTimeUp]);
+        r.g_next.work += rec[kRecNextWork];
+      }
+      r.have_g = true;
+      for (int l = 0; l < L; l++) {
+        Shard& S = sh[l];
+        if (o.enc != ~0ull && (int)(o.enc & 0xff) == S.gid)  // this shard holds the level's best terminal
+          DSL_TRY(resolve_terminal(S, ~(uint64_t)S.lc.term_best, r.depth + 1, r.depth > init_depth, &o.local_best[l]));
+      }
+    } else if (!p.rep) {
+      DSL_TRY(global_sum(o.sum));
+      if (comm) {
+        stats.host_syncs++;
+        DSL_TRY(comm->allreduce_u64(&o.enc, 1, true, stream));
+      }
+    }
+    return DSL_OK;
+  }
+
+  // Step: what makes the level's result unusable ends the search with an error.
+  int check_level_errors(const SearchRun& r, const LevelOutcome& o) {
+    if (o.sum.err_overflow) {
+      set_error("a successor exceeded the packed state's bounds (" + std::to_string(o.sum.err_overflow) + " times)");
+      return DSL_ERR_STATE_OVERFLOW;
+    }
+    if (o.sum.err_table) {
+      set_error("visited table full: raise table_log2_slots");
+      return DSL_ERR_TABLE_FULL;
+    }
+    if (o.sum.err_frontier) {
+      set_error("next frontier exceeds capacity");
+      return DSL_ERR_FRONTIER_FULL;
+    }
+    if (hset.max_frontier_states > 0 && o.sum.rows > hset.max_frontier_states) {
+      set_error("the frontier of depth " + std::to_string(r.depth + 1) + " holds " + std::to_string(o.sum.rows) +
+                " states, more than max_frontier_states");
+      return DSL_ERR_FRONTIER_FULL;
+    }
+    return DSL_OK;
+  }
+
+  // Step: the level enters the search's counts (a level the deadline cut short ends the search
+  // here), the watches' census and witnesses, and the cost model.
+  int account_level(SearchRun& r, const LevelPlan& p, const LevelOutcome& o) {
+    const LevelTotals& sum = o.sum;
+    if (sum.parents) avg_events_x16 = std::max<uint64_t>(16, (sum.work * 16 + sum.parents - 1) / sum.parents);
+    r.successors += sum.successors;
+    r.total_states += sum.new_states;
+    progress_states = r.total_states;
+    // as `states`: also of a level that is not completed
+    for (int w = 0; w < r.n_watch; w++) r.census_total[w] += sh[0].lc.watch[w];
+    if (o.level_tup && o.enc == ~0ull) {
+      // the deadline passed inside the level (Search.java:313-318): its states count, but it is
+      // not a completed depth; a terminal it found is still reported (report_terminal)
+      r.end = DSL_TIME_EXHAUSTED;
+      r.over = true;
+      return DSL_OK;
+    }
+    r.depth++;
+    if (sum.new_states)  // a completed level (single levels and queued ones alike)
+      for (int w = 0; w < r.n_watch; w++) r.census[w].push_back(sh[0].lc.watch[w]);
+    inserted += p.route ? o.max_new : sum.new_states;  // per shard (an upper bound)
+    r.prev_new = sum.new_states;
+    r.prev_work = sum.work;
+    if (sum.rows) {  // the level's parents: sum.parents when counted, else the last frontier
+      r.front_growth = (double)sum.rows / (double)(sum.parents ? sum.parents : r.prev_front);
+      r.prev_front = sum.rows;
+    }
+    if (sum.new_states) r.per_depth.push_back(sum.new_states);
+    r.max_front = std::max(r.max_front, sum.rows);
+    progress_depth = r.depth;
+    for (size_t l = 0; l < sh.size(); l++) sh[l].level_size.push_back(o.span[l]);
+    // a wanted watch's first non-zero count in a completed level: its witness, while the level's
+    // parents are still in S.cur (a level the deadline cut short is not enumerated)
+    if (dset.watch_want && !o.level_tup && watch_wanted_hit(sh[0].lc, dset.watch_want)) {
+      uint32_t hit = 0;
+      for (int w = 0; w < r.n_watch; w++)
+        if (((dset.watch_want >> w) & 1u) && sh[0].lc.watch[w]) hit |= 1u << w;
+      DSL_TRY(find_witnesses(sh[0], hit, r.depth, r.depth - 1 > init_depth, r.wit));
+      dset.watch_want &= ~hit;  // later levels queue as before
+    }
+    const double lms = ms_since(p.lt0);
+    r.level_ms_max = std::max(r.level_ms_max, lms);
+    // the cost model (auto replicate_below): c from levels in the throughput regime, X from the
+    // sharded levels that allocated nothing (a first search grows its buffers)
+    if (!p.queued && o.kms > 0) {
+      uint64_t lw = 0;
+      for (auto& S : sh) lw += S.lc.work_items;
+      if (lw >= 65536) {
+        const double c = (double)o.kms * 1e6 / (double)lw;
+        cost_c_ns = cost_c_ns > 0 ? std::min(cost_c_ns, c) : c;
+      }
+      if (p.route && n_reallocs + stats.table_rehashes == p.reallocs0) {
+        r.x_sum_us += std::max(0.0, (lms - (double)o.kms) * 1000.0);
+        r.x_levels++;
+      }
+    }
+    if (r.trace_levels)
+      fprintf(stderr, "[level] depth %d F=%llu new=%llu queued=%d wall_ms=%.4f kernel_ms=%.4f sharded=%d "
+              "routed=%llu reallocs=%llu\n", r.depth, (unsigned long long)sum.parents, (unsigned long long)sum.new_states,
+              p.queued ? 1 : 0, lms, (double)o.kms, p.route ? 1 : 0, (unsigned long long)(r.exchanged - p.exchanged0),
+              (unsigned long long)n_reallocs);
+    return DSL_OK;
+  }
+
+  // Step: the level found a terminal (o.enc): its verdict from the shard that holds it, its trace
+  // by walking the parent pointers back level by level, and (max_terminals) the level's list.
+  int report_terminal(SearchRun& r, const LevelPlan& p, const LevelOutcome& o) {
+    const int L = (int)sh.size();
+    const int wrank = (int)(o.enc & 0xff);
+    uint64_t rec[4] = {0, 0, 0, 0};
+    for (int l = 0; l < L; l++)
+      if (sh[l].gid == wrank) {
+        const TerminalRec& b = o.local_best[l];
+        rec[0] = ((uint64_t)wrank << 48) | b.parent;
+        rec[1] = b.event;
+        rec[2] = (uint64_t)b.verdict;
+        rec[3] = (uint64_t)(b.pred_index + 1);
+      }
+    if (comm && !p.rep) DSL_TRY((stats.host_syncs++, comm->bcast_u64(rec, 4, wrank, stream)));
+    const int v = (int)rec[2];
+    r.end = end_condition_of(v);
+    r.pred_index = v == V_TERM_EXCEPTION ? -1 : (int)rec[3] - 1;
+    r.term_depth = r.depth;
+    // walk parent pointers back level by level (across shards)
+    std::vector<uint32_t> evs{(uint32_t)rec[1]};
+    uint64_t ref = rec[0];
+    const int nlev = (int)sh[0].level_size.size();
+    for (int lev = nlev - 2; lev >= 1; lev--) {
+      const int src = (int)(ref >> 48);
+      const uint64_t idx = ref & ((1ull << 48) - 1);
+      uint64_t hop[2] = {0, 0};
+      for (int l = 0; l < L; l++)
+        if (sh[l].gid == src) {
+          uint64_t par;
+          uint32_t e;
+          DSL_HIP(hipMemcpy(&par, sh[l].hpar[lev] + idx, 8, hipMemcpyDeviceToHost));
+          DSL_HIP(hipMemcpy(&e, sh[l].hev[lev] + idx, 4, hipMemcpyDeviceToHost));
+          hop[0] = par;
+          hop[1] = e;
+        }
+      // a terminal of a replicated level has a local chain on every rank: no exchange
+      if (comm && !p.rep) DSL_TRY((stats.host_syncs++, comm->bcast_u64(hop, 2, src, stream)));
+      evs.push_back((uint32_t)hop[1]);
+      ref = hop[0];
+    }
+    std::reverse(evs.begin(), evs.end());
+    trace_events = evs;
+    // every terminal of this level (a level the deadline cut short is not enumerated)
+    if (hset.max_terminals > 0 && !o.level_tup)
+      DSL_TRY(list_terminals(r.depth, r.depth - 1 > init_depth, p.rep, p.owner_filter));
+    r.over = true;
+    return DSL_OK;
+  }
+
+  // Step: the level's rows checked against the host (do_checks), then they become the frontier;
+  // an empty one ends the search.
+  int advance_frontier(SearchRun& r, const LevelPlan& p, const LevelOutcome& o) {
+    const int L = (int)sh.size();
+    if (hset.do_checks != DSL_CHECKS_NONE)
+      for (int l = 0; l < L; l++) DSL_TRY(run_checks(sh[l], o.nbase[l], o.ncnt[l]));
+    if (o.sum.rows == 0) {
+      r.over = true;
+      return DSL_OK;
+    }
+    for (int l = 0; l < L; l++) {
+      Shard& S = sh[l];
+      swap_frontier(S);
+      S.seg_base = o.nbase[l];
+      S.seg_cnt = o.ncnt[l];
+      S.F = 0;
+      for (uint64_t c : o.ncnt[l]) S.F += c;
+      S.work = S.lc.next_work;
+      if (!p.queued) S.cset ^= 1;  // queued levels used the queue's counter sets
+    }
+    if (p.queued) {
+      q_pos++;
+      q_left--;
+    }
+    return DSL_OK;
+  }
+
+  // Step: the tables cleared for the next search, what the next search learns from this one, and
+  // the dsl_result with its traces replayed on the host.
+  int build_result(SearchRun& run, dsl_result** out) {
+    if (run.trace_levels) fprintf(stderr, "[levels] %.4f ms\n", ms_since(t_run0));
     // the search is over and no kernel of it is left to read the tables: zero them now, on the
     // stream, while the host assembles the result and the caller prepares the next search (whose
-    // k_setup then only writes the seed); an error return above leaves table_clean false
+    // k_setup then only writes the seed); an error return before this leaves table_clean false
     for (auto& S : sh) {
       DSL_HIP(hipMemsetAsync(S.table, 0, table_buckets * 64, stream));
       S.table_clean = true;
@@ -2550,16 +2621,14 @@ struct BfsEngine : EngineBase {
       DSL_HIP(hipMemsetAsync(qctr, 0, (size_t)(kQueue + 1) * kCtrSet, stream));
       qctr_clean = true;
     }
-    if (trace_levels)
-      fprintf(stderr, "[clear] %.4f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
-    if (x_levels) cost_x_us = x_sum_us / (double)x_levels;
-    if (L == 1) {
+    if (run.trace_levels) fprintf(stderr, "[clear] %.4f ms\n", ms_since(t_run0));
+    if (run.x_levels) cost_x_us = run.x_sum_us / (double)run.x_levels;
+    if (sh.size() == 1) {
       uint64_t want = kQueueRowsMin;
-      while (want < 4 * max_front && want < queue_span_max()) want <<= 1;
+      while (want < 4 * run.max_front && want < queue_span_max()) want <<= 1;
       q_span_want = std::max(q_span_want, want);
     }
-    stats.exchanged = exchanged;
+    stats.exchanged = run.exchanged;
     if (comm && hset.do_checks != DSL_CHECKS_NONE) {
       // every rank checked a sample of its own shards' rows: the result carries the sums (the first
       // offending event of each kind stays the one this rank found, if any)
@@ -2569,46 +2638,39 @@ struct BfsEngine : EngineBase {
       chk_nd = cv[1];
       chk_ni = cv[2];
     }
-    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     dsl_result* r = (dsl_result*)calloc(1, sizeof(dsl_result));
-    r->end_condition = end;
-    r->terminal_depth = term_depth;
-    r->predicate_index = pred_index;
-    r->states = total_states;
+    r->end_condition = run.end;
+    r->terminal_depth = run.term_depth;
+    r->predicate_index = run.pred_index;
+    r->states = run.total_states;
     r->initial_depth = init_depth;
-    r->max_depth = init_depth + (int)per_depth.size() - 1;
-    r->n_levels = (int)per_depth.size();
-    r->per_depth = (uint64_t*)malloc(sizeof(uint64_t) * per_depth.size());
-    std::memcpy(r->per_depth, per_depth.data(), sizeof(uint64_t) * per_depth.size());
-    r->elapsed_s = elapsed;
-    r->successors = successors;
-    r->new_states_inserted = total_states;
-    r->exchanged_states = exchanged;
-    r->level_ms_max = level_ms_max;
+    r->max_depth = init_depth + (int)run.per_depth.size() - 1;
+    r->n_levels = (int)run.per_depth.size();
+    r->per_depth = (uint64_t*)malloc(sizeof(uint64_t) * run.per_depth.size());
+    std::memcpy(r->per_depth, run.per_depth.data(), sizeof(uint64_t) * run.per_depth.size());
+    r->elapsed_s = ms_since(t_run0) / 1e3;
+    r->successors = run.successors;
+    r->new_states_inserted = run.total_states;
+    r->exchanged_states = run.exchanged;
+    r->level_ms_max = run.level_ms_max;
     r->checks_run = chk_run;
     r->not_deterministic = chk_nd;
     r->not_idempotent = chk_ni;
     r->first_not_deterministic = chk_first_nd;
     r->first_not_idempotent = chk_first_ni;
     r->state_bytes = sizeof(init);
-    if (term_depth >= 0) {
-      // events replayed on the host from the initial state with the same transition code
+    if (run.term_depth >= 0) {
       r->trace_len = (int)trace_events.size();
       r->trace = (dsl_event*)calloc(trace_events.size() + 1, sizeof(dsl_event));
-      typename P::State s = init, n;
-      for (size_t i = 0; i < trace_events.size(); i++) {
-        describe_event<P>(s.w, (int)trace_events[i], prm, dset, &r->trace[i]);
-        full_step<P>(s.w, (int)trace_events[i], n.w, prm, dset);
-        s = n;
-      }
+      const typename P::State s = replay_events(trace_events, r->trace);
       r->terminal_state = (uint8_t*)malloc(sizeof(init));
       std::memcpy(r->terminal_state, &s, sizeof(init));
       if (hset.max_terminals > 0) {
         // a terminal initial state, or a level the deadline cut short: the reported terminal alone
         if (term_list.empty()) {
-          term_list.push_back(ListedTrace{end == DSL_EXCEPTION_THROWN ? V_TERM_EXCEPTION
-                                          : end == DSL_INVARIANT_VIOLATED ? V_TERM_INVARIANT : V_TERM_GOAL,
-                                          pred_index, trace_events});
+          term_list.push_back(ListedTrace{run.end == DSL_EXCEPTION_THROWN ? V_TERM_EXCEPTION
+                                          : run.end == DSL_INVARIANT_VIOLATED ? V_TERM_INVARIANT : V_TERM_GOAL,
+                                          run.pred_index, trace_events});
           term_total = 1;
         }
         r->terminals_total = term_total;
@@ -2617,17 +2679,11 @@ struct BfsEngine : EngineBase {
         for (size_t t = 0; t < term_list.size(); t++) {
           const ListedTrace& lt = term_list[t];
           dsl_terminal& o = r->terminals[t];
-          o.end_condition = lt.verdict == V_TERM_EXCEPTION ? DSL_EXCEPTION_THROWN
-                            : lt.verdict == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED : DSL_GOAL_FOUND;
+          o.end_condition = end_condition_of(lt.verdict);
           o.predicate_index = lt.pred_index;
           o.trace_len = (int32_t)lt.events.size();
           o.trace = (dsl_event*)calloc(lt.events.size() + 1, sizeof(dsl_event));
-          typename P::State ts = init, tn;
-          for (size_t i = 0; i < lt.events.size(); i++) {
-            describe_event<P>(ts.w, (int)lt.events[i], prm, dset, &o.trace[i]);
-            full_step<P>(ts.w, (int)lt.events[i], tn.w, prm, dset);
-            ts = tn;
-          }
+          const typename P::State ts = replay_events(lt.events, o.trace);
           o.state = (uint8_t*)malloc(sizeof(init));
           std::memcpy(o.state, &ts, sizeof(init));
         }
@@ -2635,49 +2691,66 @@ struct BfsEngine : EngineBase {
       }
       trace_events.clear();
     }
-    if (trace_levels)
-      fprintf(stderr, "[run] %.4f ms\n",
-              std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count());
+    if (run.trace_levels) fprintf(stderr, "[run] %.4f ms\n", ms_since(t_run0));
     *out = r;
-    watch_census = std::move(census);
-    watch_total = std::move(census_total);
+    watch_census = std::move(run.census);
+    watch_total = std::move(run.census_total);
     // the witnesses: their events replayed on the host, as the terminal's are
-    watch_witness.assign(n_watch, WatchWitness{});
-    for (int w = 0; w < n_watch; w++) {
-      if (wit[w].depth < 0) continue;
+    watch_witness.assign(run.n_watch, WatchWitness{});
+    for (int w = 0; w < run.n_watch; w++) {
+      if (run.wit[w].depth < 0) continue;
       WatchWitness& o = watch_witness[w];
-      o.depth = wit[w].depth;
-      o.trace.resize(wit[w].events.size());
-      typename P::State ws = init, wn;
-      for (size_t i = 0; i < wit[w].events.size(); i++) {
-        describe_event<P>(ws.w, (int)wit[w].events[i], prm, dset, &o.trace[i]);
-        full_step<P>(ws.w, (int)wit[w].events[i], wn.w, prm, dset);
-        ws = wn;
-      }
+      o.depth = run.wit[w].depth;
+      o.trace.resize(run.wit[w].events.size());
+      const typename P::State ws = replay_events(run.wit[w].events, o.trace.data());
       o.state.assign((const uint8_t*)&ws, (const uint8_t*)&ws + sizeof(init));
     }
     return DSL_OK;
   }
 
+  // One attempt of run(). A fresh SearchRun per attempt: a restarted search starts from zero.
+  int run_once(dsl_result** out) {
+    SearchRun r;
+    DSL_TRY(prepare_search(r));
+    DSL_TRY(seed_search(r));
+    if ((int)(r.init_enc >> 32) >= V_TERM_EXCEPTION) {  // the initial state is terminal: no level runs
+      r.end = end_condition_of((int)(r.init_enc >> 32));
+      r.pred_index = (int)(r.init_enc & 0xffffffffu) - 1;
+      r.term_depth = init_depth;
+      r.over = true;
+    }
+    while (!r.over) {
+      LevelPlan p;
+      DSL_TRY(agree_frontier(r, p));
+      if (r.over) break;
+      DSL_TRY(start_queue(r, p));
+      DSL_TRY(reserve_capacity(r, p));
+      DSL_TRY(launch_levels(r, p));
+      LevelOutcome o(sh.size());
+      DSL_TRY(read_counters(r, p, o));
+      DSL_TRY(fold_totals(r, p, o));
+      DSL_TRY(check_level_errors(r, o));
+      DSL_TRY(account_level(r, p, o));
+      if (r.over) break;
+      if (o.enc != ~0ull)
+        DSL_TRY(report_terminal(r, p, o));
+      else
+        DSL_TRY(advance_frontier(r, p, o));
+    }
+    return build_result(r, out);
+  }
+
   // Search.dfs on the device (k_dfs): see dsl_run_dfs in include/dslabs_hip.h.
   int run_dfs(const dsl_dfs_config& c, dsl_result** out) override {
-    auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     clear_census();
     (void)hipGetLastError();
     if (W != 1) {
       set_error("random DFS runs on a single shard");
       return DSL_ERR_ARG;
     }
-    if (!stream) {
-      if (cfg.device >= 0) DSL_HIP(hipSetDevice(cfg.device));
-      DSL_HIP(hipStreamCreateWithFlags(&stream, hipStreamNonBlocking));
-      DSL_HIP(hipEventCreate(&ev0));
-      DSL_HIP(hipEventCreate(&ev1));
-    }
-    if (!have_init) {
-      uint8_t tmp[sizeof(init)];
-      DSL_TRY(get_initial(tmp, sizeof(init)));
-    }
+    DSL_TRY(ensure_stream());
+    DSL_TRY(ensure_init());
     const uint64_t np = c.probes > 0 ? (uint64_t)c.probes : 65536;
     const int steps = c.steps_per_launch > 0 ? c.steps_per_launch : 64;
     const int tcap = hset.max_depth >= 0 ? std::max(1, hset.max_depth - init_depth + 1)
@@ -2732,7 +2805,7 @@ struct BfsEngine : EngineBase {
       const int v = judge_view<P>(v0, prm, dset, init_depth, &pi);
       if (v >= V_TERM_EXCEPTION) {
         dsl_result* r = (dsl_result*)calloc(1, sizeof(dsl_result));
-        r->end_condition = v == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED : DSL_GOAL_FOUND;
+        r->end_condition = end_condition_of(v);
         r->terminal_depth = init_depth;
         r->predicate_index = pi;
         r->states = 1;
@@ -2760,26 +2833,23 @@ struct BfsEngine : EngineBase {
       }
       if (hf[0]) break;
       if (c.max_probes > 0 && hc[1] >= (uint64_t)c.max_probes) break;
-      const double el = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_start).count();
-      if (hset.max_time_ms > 0 && el > hset.max_time_ms) break;
+      if (hset.max_time_ms > 0 && ms_since(t_start) > hset.max_time_ms) break;
       if (hset.max_time_ms <= 0 && c.max_probes <= 0) {
         set_error("random DFS needs a time limit (maxTimeSecs) or a probe budget");
         return DSL_ERR_ARG;
       }
     }
-    const double elapsed = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
     dsl_result* r = (dsl_result*)calloc(1, sizeof(dsl_result));
     r->states = hc[0];
     r->initial_depth = init_depth;
-    r->elapsed_s = elapsed;
+    r->elapsed_s = ms_since(t_start) / 1e3;
     r->successors = hc[0];
     r->state_bytes = sizeof(init);
     r->terminal_depth = -1;
     r->predicate_index = -1;
     if (hf[0]) {
       const int v = hf[1], depth = hf[3];
-      end = v == V_TERM_EXCEPTION ? DSL_EXCEPTION_THROWN : v == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED
-                                                                                 : DSL_GOAL_FOUND;
+      end = end_condition_of(v);
       r->predicate_index = v == V_TERM_EXCEPTION ? -1 : hf[2];
       const uint64_t who = (uint64_t)(hf[0] - 1);
       std::vector<uint32_t> evs(std::min(depth, tcap));
@@ -2788,12 +2858,7 @@ struct BfsEngine : EngineBase {
       r->max_depth = r->terminal_depth;
       r->trace_len = (int)evs.size();
       r->trace = (dsl_event*)calloc(evs.size() + 1, sizeof(dsl_event));
-      typename P::State s = init, n;
-      for (size_t i = 0; i < evs.size(); i++) {  // replayed on the host with the same transitions
-        describe_event<P>(s.w, (int)evs[i], prm, dset, &r->trace[i]);
-        full_step<P>(s.w, (int)evs[i], n.w, prm, dset);
-        s = n;
-      }
+      typename P::State s = replay_events(evs, r->trace);
       if (!c.no_minimize) {  // RandomDFS reports the minimized trace (checkState(s, true))
         TraceTool<P> tt(prm, dset);
         std::vector<dsl_event> ev(r->trace, r->trace + r->trace_len);
@@ -2817,10 +2882,7 @@ struct BfsEngine : EngineBase {
   // dsl_human_readable_trace: SearchState.humanReadableTrace on the host (replay.hpp).
   int human_readable(const dsl_event* tr, int n, dsl_result** out) override {
     clear_census();
-    if (!have_init) {
-      uint8_t tmp[sizeof(init)];
-      DSL_TRY(get_initial(tmp, sizeof(init)));
-    }
+    DSL_TRY(ensure_init());
     TraceTool<P> tt(prm, dset);
     std::vector<dsl_event> evs(tr, tr + n);
     typename P::State last = init;
@@ -2854,12 +2916,9 @@ struct BfsEngine : EngineBase {
 
   // dsl_replay: TraceReplaySearch on the host (replay.hpp).
   int replay(const dsl_event* tr, int n, int minimize, dsl_result** out) override {
-    const auto t_start = std::chrono::steady_clock::now();
+    const auto t_start = Clock::now();
     clear_census();
-    if (!have_init) {
-      uint8_t tmp[sizeof(init)];
-      DSL_TRY(get_initial(tmp, sizeof(init)));
-    }
+    DSL_TRY(ensure_init());
     using Step = typename TraceTool<P>::Step;
     TraceTool<P> tt(prm, dset);
     Step cur{init, false};
@@ -2888,9 +2947,7 @@ struct BfsEngine : EngineBase {
     }
     const bool term = v >= V_TERM_EXCEPTION;
     dsl_result* r = (dsl_result*)calloc(1, sizeof(dsl_result));
-    r->end_condition = !term ? DSL_SPACE_EXHAUSTED
-                             : v == V_TERM_EXCEPTION ? DSL_EXCEPTION_THROWN
-                                                     : v == V_TERM_INVARIANT ? DSL_INVARIANT_VIOLATED : DSL_GOAL_FOUND;
+    r->end_condition = term ? end_condition_of(v) : DSL_SPACE_EXHAUSTED;
     r->predicate_index = term && v != V_TERM_EXCEPTION ? pi : -1;
     r->terminal_depth = term ? init_depth + (int)evs.size() : -1;
     r->max_depth = init_depth + (int)evs.size();
@@ -2902,7 +2959,7 @@ struct BfsEngine : EngineBase {
     if (!evs.empty()) std::memcpy(r->trace, evs.data(), evs.size() * sizeof(dsl_event));
     r->terminal_state = (uint8_t*)malloc(sizeof(init));
     std::memcpy(r->terminal_state, &cur.s, sizeof(init));
-    r->elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_start).count();
+    r->elapsed_s = ms_since(t_start) / 1e3;
     *out = r;
     return DSL_OK;
   }

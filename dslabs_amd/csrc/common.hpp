@@ -110,7 +110,7 @@ struct DevSettings {
   // the watches that want a witness and have none yet (dsl_set_watch_witnesses; bit w = watch w):
   // the level queue stops after a level that counted one of them (watch_wanted_hit), and
   // k_watch_witness selects among them. Behind everything else, as the watches are; the engine
-  // sets it per launch (BfsEngine::run_once), resolve_settings leaves it 0.
+  // sets it per launch (BfsEngine::seed_search, account_level), resolve_settings leaves it 0.
   uint32_t watch_want;
   uint32_t pad_watch;
 };

@@ -512,6 +512,15 @@ struct BfsEngine : EngineBase {
     }
     return t;
   }
+  // The launch shape of a reexpand_level pass over shard S's frontier: a wave per chunk of
+  // mat_per_max parents. At least one workgroup: over an empty frontier it visits nothing.
+  struct PassShape { SegTable segs; int blocks; size_t lds; };
+  static PassShape reexpand_shape(const Shard& S) {
+    constexpr int per = mat_per_max<P>(), nwv = kBlock / 64;
+    PassShape s{frontier_segs(S, per), 0, (size_t)nwv * per * NW * 4};
+    s.blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((s.segs.chunk0[s.segs.n] + nwv - 1) / nwv, 4096));
+    return s;
+  }
   // The next frontier becomes the current one (flip: which buffer of each pair is `cur`).
   static void swap_frontier(Shard& S) {
     std::swap(S.cur, S.next);
@@ -1015,8 +1024,8 @@ struct BfsEngine : EngineBase {
     ListArgs<P> a{};
     a.cur = S.cur;
     a.cur_fp = S.cur_fp;
-    const int per = mat_per_max<P>();
-    a.segs = frontier_segs(S, per);
+    const PassShape shape = reexpand_shape(S);
+    a.segs = shape.segs;
     a.me = S.gid;
     a.W = W;
     a.owner_filter = owner_filter ? 1 : 0;
@@ -1027,16 +1036,11 @@ struct BfsEngine : EngineBase {
     a.out = out;
     a.cap = cap;
     a.ctr = ctr;
-    const uint64_t nchunks = a.segs.chunk0[a.segs.n];
     unsigned long long h[2] = {0, 0};
-    if (nchunks) {
-      const int blocks = (int)std::min<uint64_t>((nchunks + kBlock / 64 - 1) / (kBlock / 64), 4096);
-      const size_t lds = (size_t)(kBlock / 64) * per * NW * 4;
-      hipLaunchKernelGGL(k_list_terminals<P>, dim3(blocks), dim3(kBlock), lds, stream, a, prm, dset);
-      DSL_HIP(hipGetLastError());
-      DSL_HIP(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, stream));
-      DSL_TRY(hsync());
-    }
+    hipLaunchKernelGGL(k_list_terminals<P>, dim3(shape.blocks), dim3(kBlock), shape.lds, stream, a, prm, dset);
+    DSL_HIP(hipGetLastError());
+    DSL_HIP(hipMemcpyAsync(h, ctr, 16, hipMemcpyDeviceToHost, stream));
+    DSL_TRY(hsync());
     *count = h[0];
     *full = h[1];
     recs.resize(std::min<uint64_t>(h[0], cap));
@@ -1188,22 +1192,19 @@ struct BfsEngine : EngineBase {
     WitnessArgs<P> a{};
     a.cur = S.cur;
     a.cur_fp = S.cur_fp;
-    const int per = mat_per_max<P>();
-    a.segs = frontier_segs(S, per);
+    const PassShape shape = reexpand_shape(S);
+    a.segs = shape.segs;
     a.incremental = incremental ? 1 : 0;
     a.want = want;
     a.best = best;
     a.out = out;
     a.cap = cap;
     a.n_out = best + DSL_MAX_WATCHES;
-    const uint64_t nchunks = a.segs.chunk0[a.segs.n];
-    const int blocks = (int)std::max<uint64_t>(1, std::min<uint64_t>((nchunks + kBlock / 64 - 1) / (kBlock / 64), 4096));
-    const size_t lds = (size_t)(kBlock / 64) * per * NW * 4;
     unsigned long long h[DSL_MAX_WATCHES + 1] = {};
     std::vector<WitnessRec> recs;
     for (int pass = 0; pass < 2; pass++) {  // the second only when the records ran past their room
       for (a.find = pass; a.find < 2; a.find++) {
-        hipLaunchKernelGGL(k_watch_witness<P>, dim3(blocks), dim3(kBlock), lds, stream, a, prm, dset);
+        hipLaunchKernelGGL(k_watch_witness<P>, dim3(shape.blocks), dim3(kBlock), shape.lds, stream, a, prm, dset);
         DSL_HIP(hipGetLastError());
       }
       DSL_HIP(hipMemcpyAsync(h, best, sizeof(h), hipMemcpyDeviceToHost, stream));
@@ -1442,7 +1443,7 @@ struct BfsEngine : EngineBase {
           rcv[l] = S.rep_in;
         }
         DSL_TRY(xround(snd, so, sb, rcv, ro, rb));
-        for (auto& S : sh) DSL_TRY(launch_materialize(S, depth, true, nullptr, S.out_key, S.out_item, S.rep_in, S.cap_fp));
+        for (auto& S : sh) DSL_TRY(launch_materialize(S, depth, true, nullptr, S.out_item, S.rep_in, S.cap_fp));
       }
     }
     std::vector<uint64_t> extra(L, 0);
@@ -1516,8 +1517,8 @@ struct BfsEngine : EngineBase {
   // k_new_list + k_materialize of shard S: the new ones among its routed records (the fast path's
   // sub-slabs with device counts, or host counts cnt[d] of regions of `cap` records), appended at
   // seg_span + uns_room (next_size counts them across calls).
-  int launch_materialize(Shard& S, int depth, bool dev, const uint64_t* cnt, const Fp* sent_key,
-                         const uint64_t* sent_item, const uint8_t* reply, uint64_t cap) {
+  int launch_materialize(Shard& S, int depth, bool dev, const uint64_t* cnt, const uint64_t* sent_item,
+                         const uint8_t* reply, uint64_t cap) {
     const size_t lv = S.level_size.size();
     NewListArgs na{};
     na.reply = reply;
@@ -1537,7 +1538,6 @@ struct BfsEngine : EngineBase {
     hipLaunchKernelGGL(k_new_list, dim3(groups, slab_gy(groups, per)), dim3(kBlock), 0, stream, na);
     DSL_HIP(hipGetLastError());
     MaterializeArgs<P> ma{};
-    ma.sent_key = sent_key;
     ma.sent_item = sent_item;
     ma.list = S.newl;
     ma.n_list = reinterpret_cast<const unsigned long long*>(S.nl_ctr);
@@ -1693,7 +1693,7 @@ struct BfsEngine : EngineBase {
           Shard& S = sh[l];
           uint64_t cnt[kMaxShards] = {0};
           for (int d = 0; d < W; d++) cnt[d] = rs[S.gid][d];
-          DSL_TRY(launch_materialize(S, depth, false, cnt, S.out2, S.out2_item, S.rep2, S.rs_cap));
+          DSL_TRY(launch_materialize(S, depth, false, cnt, S.out2_item, S.rep2, S.rs_cap));
         }
       }
     }

@@ -467,6 +467,12 @@ __device__ __forceinline__ bool lane_emit(bool active, const uint32_t* pw, const
   return __ballot(coll) != 0ull;
 }
 
+// A work item kept for later (the spill, route-spill and routed-item lists): (parent << 20 | event),
+// the parent's index in the current frontier and the event's index among its enabled events.
+// k_level packs them where it lists them.
+__device__ __forceinline__ uint64_t item_parent(uint64_t item) { return item >> 20; }
+__device__ __forceinline__ int item_event(uint64_t item) { return (int)(item & 0xfffff); }
+
 template <class P>
 struct LevelArgs {
   const uint32_t* cur;       // frontier rows of kWords (row ranges in `segs`)
@@ -603,6 +609,16 @@ __device__ __forceinline__ void stage_rows_dma(const uint4* src, uint32_t* dst, 
         __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + j * U + b + lane),
                                          (__attribute__((address_space(3))) void*)(dst + j * SP + 4 * b), 16, 0, 0);
   }
+}
+
+// Copies n16 contiguous 16-byte units into ONE wave's LDS area with LDS-DMA, 64 units per
+// wave-instruction (a wave that stages its own chunk: the re-expansion pass). No wait here.
+__device__ __forceinline__ void stage_wave_lds(const uint4* src, uint32_t* dst, int n16) {
+  const int lane = __lane_id();
+  for (int b = 0; b < n16; b += 64)
+    if (b + lane < n16)
+      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + b + lane),
+                                       (__attribute__((address_space(3))) void*)(dst + 4 * b), 16, 0, 0);
 }
 
 // Terminal candidates of a level are reduced EXACTLY by priority (EXCEPTION > INVARIANT > GOAL,
@@ -998,7 +1014,8 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
               if (!noop) {
                 f = delta_fingerprint_cached<P>(fp_xor(fps[j], nh[j * P::kNodes + dnode]), d);
                 // the changed node's words go through LDS: a view pointing at the register
-                // array would take its address and push the whole delta into scratch
+                // array would take its address and push the whole delta into scratch (the cold
+                // kernels' successor_view does this and builds the view below in one place)
 #pragma unroll
                 for (int q = 0; q < P::kNodeWords; q++) my_nw[q] = d.nw[q];
               }
@@ -1216,8 +1233,8 @@ __global__ void __launch_bounds__(kBlock) k_unspill(const uint64_t* items, uint6
     d.out.n = 0;
     d.keep = 0;
     if (i < n) {
-      parent = items[i] >> 20;
-      const int k = (int)(items[i] & 0xfffff);
+      parent = item_parent(items[i]);
+      const int k = item_event(items[i]);
       const uint32_t* w = cur + parent * NW;
       delta_step<P>(w, k, d, prm, set);
       const uint64_t idx = base_idx + i;
@@ -1482,8 +1499,8 @@ __global__ void __launch_bounds__(kBlock) k_respill(const uint64_t* items, uint6
   constexpr int NW = Layout<P>::kWords;
   const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
   for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const uint64_t parent = items[i] >> 20;
-    const int k = (int)(items[i] & 0xfffff);
+    const uint64_t parent = item_parent(items[i]);
+    const int k = item_event(items[i]);
     const uint32_t* w = cur + parent * NW;
     Delta<P> d;
     delta_step<P>(w, k, d, prm, set);  // deterministic: the successor k_level fingerprinted
@@ -1574,8 +1591,7 @@ __global__ void __launch_bounds__(kBlock) k_new_list(NewListArgs a) {
 
 template <class P>
 struct MaterializeArgs {
-  const Fp* sent_key;                // (unused since round 6: the fingerprint is recomputed from the parent's)
-  const uint64_t* sent_item;         // ... and their (parent << 20 | event) items
+  const uint64_t* sent_item;         // the routed records' (parent << 20 | event) items
   const uint64_t* list;              // the slots of the new ones (k_new_list)
   const unsigned long long* n_list;
   const uint32_t* cur;
@@ -1604,6 +1620,32 @@ template <class P>
 constexpr int mat_per_max() {
   constexpr int r = 8192 / (Layout<P>::kWords * 4);
   return r < 8 ? 8 : r > 64 ? 64 : r;
+}
+
+// The judge's view of the successor `d` of the parent row `w`, for the cold kernels (k_level
+// builds its own inside its phases). The changed node's words and the kept sends go through this
+// lane's slice of the workgroup's s_nodew / s_sends: a view pointing at the delta's register
+// arrays would take their address and push the whole delta into scratch.
+template <class P>
+__device__ __forceinline__ NodeView successor_view(const uint32_t* w, const Delta<P>& d, uint32_t row_hits,
+                                                   const DevSettings& set, uint32_t* s_nodew,
+                                                   typename P::Rec* s_sends) {
+  uint32_t* my_nw = s_nodew + threadIdx.x * P::kNodeWords;
+#pragma unroll
+  for (int q = 0; q < P::kNodeWords; q++) my_nw[q] = d.nw[q];
+  NodeView view{w, P::kNodeWords, d.node, my_nw};
+  if constexpr (NetPreds<P>::value) {
+    typename P::Rec* ms = s_sends + threadIdx.x * P::kMaxSends;
+    int c = 0;
+#pragma unroll
+    for (int q = 0; q < P::kMaxSends; q++)
+      if ((d.keep >> q) & 1u) ms[c++] = d.out.r[q];
+    view.sends = ms;
+    view.nsends = c;
+  }
+  if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
+  view.row_hits = row_hits;
+  return view;
 }
 
 template <class P>
@@ -1644,8 +1686,8 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
     if (act) {
       slot = a.list[i];
       const uint64_t item = a.sent_item[slot];
-      parent = item >> 20;
-      k = (int)(item & 0xfffff);
+      parent = item_parent(item);
+      k = item_event(item);
     }
     MAT_PH(0);  // (the loads' latency shows in the staging phase, their first use)
     // the wave's parent rows into LDS with LDS-DMA (no register round trip: a load-then-store
@@ -1693,21 +1735,7 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
       // source keeps no 16-byte copy of them)
       f = delta_fingerprint<P>(w, a.cur_fp[parent], d);
       int pi = -1;
-      uint32_t* my_nw = s_nodew + threadIdx.x * P::kNodeWords;
-#pragma unroll
-      for (int q = 0; q < P::kNodeWords; q++) my_nw[q] = d.nw[q];
-      NodeView view{w, P::kNodeWords, d.node, my_nw};
-      if constexpr (NetPreds<P>::value) {
-        typename P::Rec* ms = s_sends + threadIdx.x * P::kMaxSends;
-        int c = 0;
-#pragma unroll
-        for (int q = 0; q < P::kMaxSends; q++)
-          if ((d.keep >> q) & 1u) ms[c++] = d.out.r[q];
-        view.sends = ms;
-        view.nsends = c;
-      }
-      if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
-      view.row_hits = row_hits;
+      const NodeView view = successor_view<P>(w, d, row_hits, set, s_nodew, s_sends);
       const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
       if (v == V_VALID) {
         if (Net<P>::size(w) + delta_new_count<P>(d) <= P::kNetCap) ship = true;
@@ -1752,20 +1780,112 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
   block_flush(s_red, &a.ctr->next_work, c_next_work);
 }
 
+// ---- a finished level's expansion again, for the cold passes that walk it a second time -----------
+// Over the level's frontier (row ranges `segs`, still in `cur`), every successor taken as new: the
+// visited table is neither read nor written. A wave takes chunks of segs.pb <= mat_per_max parents
+// (contiguous rows of one segment), stages them in LDS, counts their enabled events, and runs one
+// lane per (parent, event): delta_step, the no-op test, the successor's fingerprint from the
+// parent's and its view. `visit` is called once per batch of 64 items with the wave converged --
+// by every lane, `live` or not, so it may ballot and reserve by wave -- with
+//   (live, delta_step's code, no-op, parent index, event, parent's fingerprint, f, view);
+// f and the view are those of a live STEP_OK successor that is not a no-op, {0, 0} and empty
+// otherwise. owner_filter: only the parents shard `me` of W owns were expanded (the first
+// hash-sharded level). watches: the row pre-scan also serves the watches' network leaves.
+template <class P, class Visit>
+__device__ __forceinline__ void reexpand_level(const uint32_t* cur, const Fp* cur_fp, const SegTable& segs,
+                                               bool owner_filter, int W, int me, bool incremental, bool watches,
+                                               const typename P::Params& prm, const DevSettings& set, Visit visit) {
+  constexpr int NW = Layout<P>::kWords;
+  constexpr int PMAX = mat_per_max<P>();
+  constexpr int NWV = kBlock / 64;
+  __shared__ uint32_t s_nodew[kBlock * P::kNodeWords];
+  __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kBlock * P::kMaxSends : 1];
+  __shared__ int s_off[NWV][PMAX + 1];
+  extern __shared__ __align__(16) uint32_t s_mrows[];  // NWV x PMAX parent rows
+  const int lane = __lane_id(), wid = threadIdx.x >> 6;
+  uint32_t* wrows = s_mrows + wid * PMAX * NW;
+  int* off = s_off[wid];
+  const int per = segs.pb;  // <= PMAX (host)
+  const uint64_t nchunks = segs.chunk0[segs.n];
+  // the network leaves' scan of the parent row, where the judge will ask for it (as k_level's)
+  const bool need_row = net_needs_row(set, incremental, 0) || (watches && watch_needs_row(set));
+  for (uint64_t c = (uint64_t)blockIdx.x * NWV + wid; c < nchunks; c += (uint64_t)gridDim.x * NWV) {
+    int q = 0;
+    while (q + 1 < segs.n && c >= segs.chunk0[q + 1]) q++;
+    const uint64_t r0 = (c - segs.chunk0[q]) * (uint64_t)per;
+    const uint64_t p0 = segs.base[q] + r0;
+    const int nr = (int)min<uint64_t>((uint64_t)per, segs.cnt[q] - r0);
+    stage_wave_lds(reinterpret_cast<const uint4*>(cur + p0 * NW), wrows, nr * (NW / 4));
+    __builtin_amdgcn_s_waitcnt(0);
+    __builtin_amdgcn_wave_barrier();
+    // enabled events per parent, and their exclusive scan
+    int x = 0;
+    if (lane < nr && !(owner_filter && owner_of(cur_fp[p0 + lane], W) != me))
+      x = count_events<P>(wrows + lane * NW, prm, set);
+    x = (int)wave_incl_sum((uint32_t)x);
+    const int total = (int)rl32((uint32_t)x, 63);
+    if (lane < nr) off[lane + 1] = x;
+    if (lane == 0) off[0] = 0;
+    __builtin_amdgcn_wave_barrier();
+    for (int t0 = 0; t0 < total; t0 += 64) {
+      const int t = t0 + lane;
+      const bool live = t < total;
+      int rc = STEP_NULL, k = 0, j = 0;
+      bool noop = false;
+      Fp pf{0, 0}, f{0, 0};
+      NodeView view{nullptr, P::kNodeWords, -1, nullptr};
+      if (live) {
+        // the parent of item t: the last j with off[j] <= t
+        int lo = 0, hi = nr - 1;
+        while (lo < hi) {
+          const int mid = (lo + hi + 1) >> 1;
+          if (off[mid] <= t) lo = mid;
+          else hi = mid - 1;
+        }
+        j = lo;
+        k = t - off[j];
+        const uint32_t* w = wrows + j * NW;
+        Delta<P> d;
+        d.node = 0;
+        d.out.n = 0;
+        d.keep = 0;
+        uint32_t row_hits = 0;
+        if (need_row) row_hits = row_net_hits<P>(set, w);
+        pf = cur_fp[p0 + j];
+        rc = delta_step<P>(w, k, d, prm, set);
+        if (rc == STEP_OK) {
+          // a successor that changes neither its node nor the network is its parent (the events
+          // the no-op filter proves idle are among these)
+          noop = delta_new_count<P>(d) == 0 && same_words<P::kNodeWords>(d.nw, w + d.node * P::kNodeWords);
+          if (!noop) {
+            f = delta_fingerprint<P>(w, pf, d);
+            view = successor_view<P>(w, d, row_hits, set, s_nodew, s_sends);
+          }
+        }
+      }
+      // the view's pointers are functions of j and the lane: set again here, at the converged
+      // point, none is carried across the branch in a register pair (2-4 VGPRs per kernel)
+      view.base = wrows + j * NW;
+      view.over = s_nodew + threadIdx.x * P::kNodeWords;
+      if constexpr (NetPreds<P>::value) view.sends = s_sends + threadIdx.x * P::kMaxSends;
+      visit(live, rc, noop, p0 + (uint64_t)j, k, pf, f, view);
+    }
+    __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
+  }
+}
+
 // ---- every terminal of the level that ended the search (dsl_settings.max_terminals) ---------------
 // Runs once, after the terminal level, over that level's frontier (still in `cur`): the level's
 // expansion again with every successor taken as new, as the find mode of k_level does -- a
 // successor first seen at an earlier level was judged there and is not terminal (checkState is a
 // function of the state), so the visited table is neither read nor written. A kernel of its own:
 // k_level's register allocation must not move for a pass that runs once per search.
-// A wave stages up to mat_per_max parents (contiguous rows of one segment) in LDS, counts their
-// enabled events, and runs one lane per (parent, event): delta_step, the successor's fingerprint
-// from the parent's, judge_view with the level's depth and `incremental` flag. A TERMINAL state is
-// listed once: the first lane to insert its fingerprint into the pass's own scratch table (fresh
-// and empty, one CAS per probe) wins; an exceptional successor equals no other and skips the
-// table (its fingerprint: exception_key, as in k_level). A winner reserves its slot with one
-// returning atomic per wavefront; the counter runs past the list's room (the host then runs the
-// pass again at the exact size).
+// The expansion is reexpand_level's; a successor is judged (judge_view with the level's depth and
+// `incremental` flag) and a TERMINAL state is listed once: the first lane to insert its
+// fingerprint into the pass's own scratch table (fresh and empty, one CAS per probe) wins; an
+// exceptional successor equals no other and skips the table (its fingerprint: exception_key, as
+// in k_level). A winner reserves its slot with one returning atomic per wavefront; the counter
+// runs past the list's room (the host then runs the pass again at the exact size).
 struct ListedTerminal {
   TerminalRec rec;  // key: term_key of fp.hi
   Fp fp;            // the state's full fingerprint (an exceptional successor: {exception_key, parent's lo + event + 1})
@@ -1787,121 +1907,40 @@ struct ListArgs {
 
 template <class P>
 __global__ void __launch_bounds__(kBlock) k_list_terminals(ListArgs<P> a, typename P::Params prm, DevSettings set) {
-  constexpr int NW = Layout<P>::kWords;
-  constexpr int PMAX = mat_per_max<P>();
-  constexpr int NWV = kBlock / 64;
-  __shared__ uint32_t s_nodew[kBlock * P::kNodeWords];
-  __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kBlock * P::kMaxSends : 1];
-  __shared__ int s_off[NWV][PMAX + 1];
-  extern __shared__ __align__(16) uint32_t s_mrows[];  // NWV x PMAX parent rows
-  const int lane = __lane_id(), wid = threadIdx.x >> 6;
-  uint32_t* wrows = s_mrows + wid * PMAX * NW;
-  int* off = s_off[wid];
-  const int per = a.segs.pb;  // <= PMAX (host)
-  const uint64_t nchunks = a.segs.chunk0[a.segs.n];
-  for (uint64_t c = (uint64_t)blockIdx.x * NWV + wid; c < nchunks; c += (uint64_t)gridDim.x * NWV) {
-    int q = 0;
-    while (q + 1 < a.segs.n && c >= a.segs.chunk0[q + 1]) q++;
-    const uint64_t r0 = (c - a.segs.chunk0[q]) * (uint64_t)per;
-    const uint64_t p0 = a.segs.base[q] + r0;
-    const int nr = (int)min<uint64_t>((uint64_t)per, a.segs.cnt[q] - r0);
-    // the chunk's rows (contiguous) into LDS with LDS-DMA, 64 16-byte units per wave-instruction
-    const int n16 = nr * (NW / 4);
-    const uint4* src = reinterpret_cast<const uint4*>(a.cur + p0 * NW);
-    for (int b = 0; b < n16; b += 64)
-      if (b + lane < n16)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + b + lane),
-                                         (__attribute__((address_space(3))) void*)(wrows + 4 * b), 16, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    // enabled events per parent, and their exclusive scan
-    int x = 0;
-    if (lane < nr && !(a.owner_filter && owner_of(a.cur_fp[p0 + lane], a.W) != a.me))
-      x = count_events<P>(wrows + lane * NW, prm, set);
-    x = (int)wave_incl_sum((uint32_t)x);
-    const int total = (int)rl32((uint32_t)x, 63);
-    if (lane < nr) off[lane + 1] = x;
-    if (lane == 0) off[0] = 0;
-    __builtin_amdgcn_wave_barrier();
-    for (int t0 = 0; t0 < total; t0 += 64) {
-      const int t = t0 + lane;
-      const bool live = t < total;
-      bool cand = false, exc = false;
-      int tv = 0, tpi = -1, k = 0, j = 0;
-      Fp f{0, 0};
-      if (live) {
-        // the parent of item t: the last j with off[j] <= t
-        int lo = 0, hi = nr - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (off[mid] <= t) lo = mid;
-          else hi = mid - 1;
-        }
-        j = lo;
-        k = t - off[j];
-        const uint32_t* w = wrows + j * NW;
-        const Fp pf = a.cur_fp[p0 + j];
-        Delta<P> d;
-        d.node = 0;
-        d.out.n = 0;
-        d.keep = 0;
-        uint32_t row_hits = 0;  // as k_level's
-        if (net_needs_row(set, a.incremental != 0, 0)) row_hits = row_net_hits<P>(set, w);
-        const int rc = delta_step<P>(w, k, d, prm, set);
-        if (rc == STEP_OK) {
-          const int dn = delta_new_count<P>(d);
-          // a successor that changes neither its node nor the network is its parent, which was
-          // expanded: not terminal (the events the no-op filter proves idle are among these)
-          const bool noop = dn == 0 && same_words<P::kNodeWords>(d.nw, w + d.node * P::kNodeWords);
-          if (!noop) {
-            f = delta_fingerprint<P>(w, pf, d);
-            int pi = -1;
-            uint32_t* my_nw = s_nodew + threadIdx.x * P::kNodeWords;
-#pragma unroll
-            for (int i = 0; i < P::kNodeWords; i++) my_nw[i] = d.nw[i];
-            NodeView view{w, P::kNodeWords, d.node, my_nw};
-            if constexpr (NetPreds<P>::value) {
-              typename P::Rec* ms = s_sends + threadIdx.x * P::kMaxSends;
-              int n = 0;
-#pragma unroll
-              for (int i = 0; i < P::kMaxSends; i++)
-                if ((d.keep >> i) & 1u) ms[n++] = d.out.r[i];
-              view.sends = ms;
-              view.nsends = n;
-            }
-            if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
-            view.row_hits = row_hits;
-            const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
-            if (v >= V_TERM_EXCEPTION) {
-              cand = true;
-              tv = v;
-              tpi = pi;
-            }
+  reexpand_level<P>(
+      a.cur, a.cur_fp, a.segs, a.owner_filter != 0, a.W, a.me, a.incremental != 0, false, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp& pf, Fp f, const NodeView& view) {
+        bool cand = false, exc = false;
+        int tv = 0, tpi = -1;
+        if (live && rc == STEP_OK && !noop) {
+          int pi = -1;
+          const int v = judge_view<P>(view, prm, set, a.depth, &pi, a.incremental != 0);
+          if (v >= V_TERM_EXCEPTION) {
+            cand = true;
+            tv = v;
+            tpi = pi;
           }
-        } else if (rc == STEP_EXCEPTION) {
+        } else if (live && rc == STEP_EXCEPTION) {
           cand = exc = true;
           tv = V_TERM_EXCEPTION;
           f = Fp{exception_key(pf, k), pf.lo + (uint64_t)k + 1ull};
-        }  // STEP_OVERFLOW: the level reported it
-      }
-      bool win = exc;
-      if (cand && !exc) {
-        const int ins = table_insert(a.scratch, f);
-        win = ins == INS_NEW;
-        if (ins == INS_FULL) atomicAdd(&a.ctr[1], 1ull);
-      }
-      const unsigned long long slot = wave_reserve(&a.ctr[0], win);
-      if (win && slot < a.cap)
-        a.out[slot] = ListedTerminal{TerminalRec{tv, tpi, (uint32_t)k, 0u, p0 + (uint64_t)j, term_key(tv, f.hi)}, f};
-    }
-    __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
-  }
+        }  // a no-op is its parent, which was expanded: not terminal; STEP_OVERFLOW: the level reported it
+        bool win = exc;
+        if (cand && !exc) {
+          const int ins = table_insert(a.scratch, f);
+          win = ins == INS_NEW;
+          if (ins == INS_FULL) atomicAdd(&a.ctr[1], 1ull);
+        }
+        const unsigned long long slot = wave_reserve(&a.ctr[0], win);
+        if (win && slot < a.cap)
+          a.out[slot] = ListedTerminal{TerminalRec{tv, tpi, (uint32_t)k, 0u, parent, term_key(tv, f.hi)}, f};
+      });
 }
 
 // ---- a witness of each watch's first hit (dsl_set_watch_witnesses) ---------------------------------
 // Runs after a completed level in which a watch that wants a witness was counted for the first
-// time, over that level's frontier (still in `cur`): the level's expansion again, wave by wave as
-// k_list_terminals does it, with every successor taken as new. This is sound for the same reason:
+// time, over that level's frontier (still in `cur`): the level's expansion again (reexpand_level)
+// with every successor taken as new. This is sound for k_list_terminals' reason:
 // a successor first discovered at an earlier depth had its watches evaluated there and the watch
 // did not hold, or this would not be the first level with a non-zero count -- so every successor of
 // this level in which the watch holds was newly discovered in it, and the visited table is neither
@@ -1939,18 +1978,6 @@ struct WitnessArgs {
 
 template <class P>
 __global__ void __launch_bounds__(kBlock) k_watch_witness(WitnessArgs<P> a, typename P::Params prm, DevSettings set) {
-  constexpr int NW = Layout<P>::kWords;
-  constexpr int PMAX = mat_per_max<P>();
-  constexpr int NWV = kBlock / 64;
-  __shared__ uint32_t s_nodew[kBlock * P::kNodeWords];
-  __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kBlock * P::kMaxSends : 1];
-  __shared__ int s_off[NWV][PMAX + 1];
-  extern __shared__ __align__(16) uint32_t s_mrows[];  // NWV x PMAX parent rows
-  const int lane = __lane_id(), wid = threadIdx.x >> 6;
-  uint32_t* wrows = s_mrows + wid * PMAX * NW;
-  int* off = s_off[wid];
-  const int per = a.segs.pb;  // <= PMAX (host)
-  const uint64_t nchunks = a.segs.chunk0[a.segs.n];
   const bool find = a.find != 0;
   // per watch (wave-uniform, constant indices: registers): find = 0 the wave's minimum so far,
   // find = 1 the key to look for
@@ -1958,102 +1985,34 @@ __global__ void __launch_bounds__(kBlock) k_watch_witness(WitnessArgs<P> a, type
   uint32_t seen = 0;  // find = 0: the watches with a candidate in this wave
 #pragma unroll
   for (int q = 0; q < DSL_MAX_WATCHES; q++) wkey[q] = find ? ~a.best[q] : ~0ull;
-  const bool need_row = net_needs_row(set, a.incremental != 0, 0) || watch_needs_row(set);
-  for (uint64_t c = (uint64_t)blockIdx.x * NWV + wid; c < nchunks; c += (uint64_t)gridDim.x * NWV) {
-    int sq = 0;
-    while (sq + 1 < a.segs.n && c >= a.segs.chunk0[sq + 1]) sq++;
-    const uint64_t r0 = (c - a.segs.chunk0[sq]) * (uint64_t)per;
-    const uint64_t p0 = a.segs.base[sq] + r0;
-    const int nr = (int)min<uint64_t>((uint64_t)per, a.segs.cnt[sq] - r0);
-    // the chunk's rows (contiguous) into LDS with LDS-DMA, 64 16-byte units per wave-instruction
-    const int n16 = nr * (NW / 4);
-    const uint4* src = reinterpret_cast<const uint4*>(a.cur + p0 * NW);
-    for (int b = 0; b < n16; b += 64)
-      if (b + lane < n16)
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src + b + lane),
-                                         (__attribute__((address_space(3))) void*)(wrows + 4 * b), 16, 0, 0);
-    __builtin_amdgcn_s_waitcnt(0);
-    __builtin_amdgcn_wave_barrier();
-    // enabled events per parent, and their exclusive scan
-    int x = 0;
-    if (lane < nr) x = count_events<P>(wrows + lane * NW, prm, set);
-    x = (int)wave_incl_sum((uint32_t)x);
-    const int total = (int)rl32((uint32_t)x, 63);
-    if (lane < nr) off[lane + 1] = x;
-    if (lane == 0) off[0] = 0;
-    __builtin_amdgcn_wave_barrier();
-    for (int t0 = 0; t0 < total; t0 += 64) {
-      const int t = t0 + lane;
-      uint32_t held = 0;
-      int k = 0, j = 0;
-      Fp f{0, 0};
-      if (t < total) {
-        // the parent of item t: the last j with off[j] <= t
-        int lo = 0, hi = nr - 1;
-        while (lo < hi) {
-          const int mid = (lo + hi + 1) >> 1;
-          if (off[mid] <= t) lo = mid;
-          else hi = mid - 1;
-        }
-        j = lo;
-        k = t - off[j];
-        const uint32_t* w = wrows + j * NW;
-        Delta<P> d;
-        d.node = 0;
-        d.out.n = 0;
-        d.keep = 0;
-        uint32_t row_hits = 0;  // as k_level's, with watches
-        if (need_row) row_hits = row_net_hits<P>(set, w);
-        const int rc = delta_step<P>(w, k, d, prm, set);
-        if (rc == STEP_OK) {
-          const int dn = delta_new_count<P>(d);
-          // a successor that changes neither its node nor the network is its parent: not new
-          const bool noop = dn == 0 && same_words<P::kNodeWords>(d.nw, w + d.node * P::kNodeWords);
-          if (!noop) {
-            f = delta_fingerprint<P>(w, a.cur_fp[p0 + j], d);
-            uint32_t* my_nw = s_nodew + threadIdx.x * P::kNodeWords;
+  reexpand_level<P>(
+      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, true, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp&, Fp f, const NodeView& view) {
+        // a no-op is its parent: not new; exceptional successors are never counted
+        uint32_t held = 0;
+        if (live && rc == STEP_OK && !noop) held = eval_watches<P>(view, prm, set) & a.want;
 #pragma unroll
-            for (int i = 0; i < P::kNodeWords; i++) my_nw[i] = d.nw[i];
-            NodeView view{w, P::kNodeWords, d.node, my_nw};
-            if constexpr (NetPreds<P>::value) {
-              typename P::Rec* ms = s_sends + threadIdx.x * P::kMaxSends;
-              int n = 0;
-#pragma unroll
-              for (int i = 0; i < P::kMaxSends; i++)
-                if ((d.keep >> i) & 1u) ms[n++] = d.out.r[i];
-              view.sends = ms;
-              view.nsends = n;
+        for (int q = 0; q < DSL_MAX_WATCHES; q++) {
+          if (!((a.want >> q) & 1u)) continue;
+          const bool h = (held >> q) & 1u;
+          if (!find) {
+            // the wave's minimum key: a scalar walk over the (few) holding lanes
+            for (unsigned long long r = __ballot(h); r; r &= r - 1) {
+              const unsigned long long y = rl64(f.hi, __ffsll((long long)r) - 1);
+              wkey[q] = y < wkey[q] ? y : wkey[q];
+              seen |= 1u << q;
             }
-            if (set.n_net) view.net_hits = delta_net_hits<P>(set, d);
-            view.row_hits = row_hits;
-            held = eval_watches<P>(view, prm, set) & a.want;
-          }
-        }  // exceptional successors are never counted; STEP_OVERFLOW: the level reported it
-      }
-      // the wave is converged here
-#pragma unroll
-      for (int q = 0; q < DSL_MAX_WATCHES; q++) {
-        if (!((a.want >> q) & 1u)) continue;
-        const bool h = (held >> q) & 1u;
-        if (!find) {
-          // the wave's minimum key: a scalar walk over the (few) holding lanes
-          for (unsigned long long r = __ballot(h); r; r &= r - 1) {
-            const unsigned long long y = rl64(f.hi, __ffsll((long long)r) - 1);
-            wkey[q] = y < wkey[q] ? y : wkey[q];
-            seen |= 1u << q;
-          }
-        } else {
-          const bool hit = h && f.hi == wkey[q];
-          if (__ballot(hit)) {
-            const unsigned long long slot = wave_reserve(a.n_out, hit);
-            if (hit && slot < a.cap) a.out[slot] = WitnessRec{p0 + (uint64_t)j, (uint32_t)k, (uint32_t)q, f};
+          } else {
+            const bool hit = h && f.hi == wkey[q];
+            if (__ballot(hit)) {
+              const unsigned long long slot = wave_reserve(a.n_out, hit);
+              if (hit && slot < a.cap) a.out[slot] = WitnessRec{parent, (uint32_t)k, (uint32_t)q, f};
+            }
           }
         }
-      }
-    }
-    __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
-  }
+      });
   if (!find) {  // lane q folds the wave's minimum of watch q: one atomic instruction per wave
+    const int lane = __lane_id();
     unsigned long long mine = 0;
 #pragma unroll
     for (int q = 0; q < DSL_MAX_WATCHES; q++) mine = (lane == q && ((seen >> q) & 1u)) ? ~wkey[q] : mine;

@@ -128,6 +128,24 @@ def test_terminal_set_equals_the_oracles(name, shards):
     _, _, oargs, want = _case(name)
     assert dict(collections.Counter(t["kind"] for t in want["terminals"])) == KINDS[name]
     r, s = _search(name, 4096, **(SHARDED if shards > 1 else {}))
+    _check_set(name, r, s, oargs, want)
+
+
+def test_terminal_level_is_the_first_sharded_level(monkeypatch, capfd):
+    """The listing pass with the owner filter on: the levels below the terminal level's frontier
+    (66 Multi-Paxos parents, six chunks of at most 12) run replicated, so the terminal level is the
+    first sharded one -- every shard holds all its parents and expands only those it owns, and the
+    pass must skip the others (parents of no work item between parents that have some)."""
+    name = "mp_expect_violation"
+    _, _, oargs, want = _case(name)
+    monkeypatch.setenv("DSL_LEVEL_TRACE", "1")
+    r, s = _search(name, 4096, virtual_shards=3, replicate_below=want["per_depth"][-2])
+    sharded = re.findall(r"^\[level\] .* sharded=(\d)", capfd.readouterr().err, re.M)
+    assert len(sharded) > 1 and sharded == ["0"] * (len(sharded) - 1) + ["1"]
+    _check_set(name, r, s, oargs, want)
+
+
+def _check_set(name, r, s, oargs, want):
     assert r.endCondition().name == want["end"]
     assert r.per_depth == want["per_depth"]
     assert r.numTerminals() == want["num_terminals"] == len(r.terminals())

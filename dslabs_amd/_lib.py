@@ -41,6 +41,8 @@ EXPORTED = [
     "dsl_kernel_stats", "dsl_result_free", "dsl_destroy", "dsl_last_error", "dsl_create_with_host_comm",
     "dsl_run_dfs", "dsl_replay", "dsl_human_readable_trace", "dsl_set_dropped",
     "dsl_set_watches", "dsl_watch_counts", "dsl_set_watch_witnesses", "dsl_watch_witness",
+    "dsl_event_class_count", "dsl_event_class_name", "dsl_event_class_is_timer", "dsl_set_event_census",
+    "dsl_event_census",
 ]
 DSL_ABI_VERSION = 6  # include/dslabs_hip.h; load() refuses a library of another layout
 
@@ -124,6 +126,14 @@ class dsl_result(ctypes.Structure):
     ]
 
 
+DSL_EVENT_CLASSES, DSL_EVENT_NODES = 15, 8  # the event census's grid (dsl_event_census)
+
+
+class dsl_event_count(ctypes.Structure):
+    _fields_ = [("events", ctypes.c_uint64), ("noops", ctypes.c_uint64), ("exceptions", ctypes.c_uint64),
+                ("fresh", ctypes.c_uint64)]
+
+
 class dsl_stats(ctypes.Structure):
     _fields_ = [("expand_ms", ctypes.c_double), ("exchange_ms", ctypes.c_double),
                 ("expand_launches", ctypes.c_uint64), ("parents", ctypes.c_uint64),
@@ -172,6 +182,12 @@ def load() -> ctypes.CDLL:
     lib.dsl_set_watch_witnesses.argtypes = [ctypes.c_void_p, ctypes.c_uint32]
     lib.dsl_watch_witness.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(ctypes.c_int32), P(dsl_event), ctypes.c_int32,
                                       P(ctypes.c_int32), P(ctypes.c_uint8), ctypes.c_size_t]
+    lib.dsl_event_class_count.argtypes = [P(dsl_protocol_desc)]
+    lib.dsl_event_class_name.argtypes = [P(dsl_protocol_desc), ctypes.c_int32]
+    lib.dsl_event_class_name.restype = ctypes.c_char_p
+    lib.dsl_event_class_is_timer.argtypes = [P(dsl_protocol_desc), ctypes.c_int32]
+    lib.dsl_set_event_census.argtypes = [ctypes.c_void_p, ctypes.c_int32]
+    lib.dsl_event_census.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(dsl_event_count), P(ctypes.c_int32)]
     lib.dsl_run.argtypes = [ctypes.c_void_p, P(P(dsl_result))]
     lib.dsl_run_dfs.argtypes = [ctypes.c_void_p, P(dsl_dfs_config), P(P(dsl_result))]
     lib.dsl_replay.argtypes = [ctypes.c_void_p, P(dsl_event), ctypes.c_int32, ctypes.c_int32, P(P(dsl_result))]

@@ -109,10 +109,16 @@ struct EngineBase {
     std::vector<uint8_t> state;
   };
   std::vector<WatchWitness> watch_witness;
+  // the event census of the last run() (dsl_set_event_census): one row per completed level,
+  // DSL_EVENT_CLASSES * DSL_EVENT_NODES cells of {events, noops, exceptions, fresh}, class-major
+  static constexpr size_t kEventWords = (size_t)DSL_EVENT_CLASSES * DSL_EVENT_NODES * 4;
+  std::vector<std::vector<uint64_t>> event_census;
+  bool event_census_on = false;
   void clear_census() {
     watch_census.clear();
     watch_total.clear();
     watch_witness.clear();
+    event_census.clear();
   }
   virtual int num_watches() const = 0;
   virtual int set_watch_witnesses(uint32_t mask) = 0;
@@ -363,6 +369,8 @@ struct BfsEngine : EngineBase {
     if (segs_host) (void)hipHostFree(segs_host);
     (void)hipFree(rehash_err);
     (void)hipFree(t0_rt);
+    (void)hipFree(ev_dev);
+    if (ev_host) (void)hipHostFree(ev_host);
     if (xhost) (void)hipHostFree(xhost);
     if (hq) (void)hipHostFree(hq);
     for (auto e : qev) (void)hipEventDestroy(e);
@@ -396,6 +404,9 @@ struct BfsEngine : EngineBase {
     }
     return rc;
   }
+  // The event census's device buffer (k_event_census's `out`) and its pinned host copy.
+  unsigned long long* ev_dev = nullptr;
+  unsigned long long* ev_host = nullptr;
   // The watches that want a witness (dsl_set_watch_witnesses): bit w = watch w.
   uint32_t witness_mask = 0;
   int num_watches() const override { return (int)hwatch.size(); }
@@ -1811,6 +1822,13 @@ struct BfsEngine : EngineBase {
                 " shards): run it with virtual_shards = 1 and world_size = 1, or clear the watches (dsl_set_watches)");
       return DSL_ERR_ARG;
     }
+    // the event census is single-shard too: a routed successor's `fresh` is its owner's answer, so
+    // the cells would be counted at the owner. Refused the same way, before any collective.
+    if (event_census_on && W > 1) {
+      set_error("the event census is not supported in a search over more than one shard (" + std::to_string(W) +
+                " shards): run it with virtual_shards = 1 and world_size = 1, or turn it off (dsl_set_event_census)");
+      return DSL_ERR_ARG;
+    }
     restart_buckets = 0;
     t_run0 = std::chrono::steady_clock::now();
     for (int attempt = 0;; attempt++) {
@@ -1864,6 +1882,10 @@ struct BfsEngine : EngineBase {
     std::vector<std::vector<uint64_t>> census;
     std::vector<uint64_t> census_total;
     std::vector<WitnessTrace> wit;  // the witnesses of this attempt (a restarted search finds them again)
+    // the event census of this attempt (a restarted search counts from zero): one row per completed
+    // level; ev_pending: this level's pass ran and its counts came back with the level's counters
+    std::vector<std::vector<uint64_t>> events;
+    bool ev_pending = false;
     // a sharded level's gathered records already hold the next level's global frontier size, work
     // and time-up flag (LevelPlan::g): no collective at the top of that next level
     bool have_g = false;
@@ -1967,7 +1989,13 @@ struct BfsEngine : EngineBase {
     q_left = 0;
     q_pos = 0;
     // do_checks reads every level's rows right after the level: no device-side queue of levels
-    r.use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE;
+    // ... and the event census runs its pass before every level's k_level, on the table as it
+    // stands then
+    r.use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE && !event_census_on;
+    if (event_census_on) {
+      if (!ev_dev) DSL_HIP(hipMalloc(&ev_dev, kEventWords * 8));
+      if (!ev_host) DSL_HIP(hipHostMalloc(&ev_host, kEventWords * 8));
+    }
     chk_run = chk_nd = chk_ni = 0;
     chk_first_nd = chk_first_ni = dsl_event{};
     if (const char* qr = getenv("DSL_QUEUE_ROWS")) q_rows_forced = std::max<uint64_t>(kSegs, strtoull(qr, nullptr, 10) / kSegs * kSegs);
@@ -2202,10 +2230,36 @@ struct BfsEngine : EngineBase {
     return DSL_OK;
   }
 
+  // The event census's pass over the level about to run (single shard, never queued): its buffer
+  // zeroed on the stream, then k_event_census over the frontier -- after ensure_table and before
+  // the level's k_level, so the table holds exactly the states of the depths up to the frontier's.
+  // (A level the deadline forbids is never reached: agree_frontier ended the search before it.)
+  int enqueue_event_census(SearchRun& r) {
+    r.ev_pending = false;
+    if (!event_census_on) return DSL_OK;
+    Shard& S = sh[0];
+    if (S.F == 0) return DSL_OK;
+    DSL_HIP(hipMemsetAsync(ev_dev, 0, kEventWords * 8, stream));
+    const PassShape shape = reexpand_shape(S);
+    CensusArgs<P> a{};
+    a.cur = S.cur;
+    a.cur_fp = S.cur_fp;
+    a.segs = shape.segs;
+    a.incremental = r.depth > init_depth ? 1 : 0;
+    a.table = tbl;
+    a.table.slots = S.table;
+    a.out = ev_dev;
+    hipLaunchKernelGGL(k_event_census<P>, dim3(shape.blocks), dim3(kBlock), shape.lds, stream, a, prm, dset);
+    DSL_HIP(hipGetLastError());
+    r.ev_pending = true;
+    return DSL_OK;
+  }
+
   // Step: one k_level per shard with a frontier, bracketed by the timing events (a queued level
   // was launched with its queue).
-  int launch_levels(const SearchRun& r, const LevelPlan& p) {
+  int launch_levels(SearchRun& r, const LevelPlan& p) {
     if (p.queued) return DSL_OK;
+    DSL_TRY(enqueue_event_census(r));
     DSL_HIP(hipEventRecord(ev0, stream));
     for (auto& S : sh) {
       if (S.F == 0) continue;
@@ -2280,6 +2334,8 @@ struct BfsEngine : EngineBase {
         for (auto& S : sh)
           DSL_HIP(hipMemcpyAsync(S.hctr, S.ctrbuf + S.cset * kCtrSet, kCtrSegOff + 8 * S.nseg * kSegStride,
                                  hipMemcpyDeviceToHost, stream));
+        if (r.ev_pending)  // the event census's counts, with the level's own counters: no round trip of their own
+          DSL_HIP(hipMemcpyAsync(ev_host, ev_dev, kEventWords * 8, hipMemcpyDeviceToHost, stream));
         DSL_TRY(hsync());
         for (int l = 0; l < L; l++) {
           Shard& S = sh[l];
@@ -2485,6 +2541,9 @@ struct BfsEngine : EngineBase {
     r.depth++;
     if (sum.new_states)  // a completed level (single levels and queued ones alike)
       for (int w = 0; w < r.n_watch; w++) r.census[w].push_back(sh[0].lc.watch[w]);
+    // the event census's row of a completed level (one that found a terminal before the deadline
+    // cut it short is partial: no row)
+    if (r.ev_pending && !o.level_tup) r.events.emplace_back(ev_host, ev_host + kEventWords);
     inserted += p.route ? o.max_new : sum.new_states;  // per shard (an upper bound)
     r.prev_new = sum.new_states;
     r.prev_work = sum.work;
@@ -2694,6 +2753,7 @@ struct BfsEngine : EngineBase {
     if (run.trace_levels) fprintf(stderr, "[run] %.4f ms\n", ms_since(t_run0));
     *out = r;
     watch_census = std::move(run.census);
+    event_census = std::move(run.events);
     watch_total = std::move(run.census_total);
     // the witnesses: their events replayed on the host, as the terminal's are
     watch_witness.assign(run.n_watch, WatchWitness{});

@@ -533,6 +533,67 @@ int dsl_watch_witness(dsl_engine* e, int32_t watch, int32_t* depth, dsl_event* t
   return DSL_OK;
 }
 
+int dsl_event_class_count(const dsl_protocol_desc* proto) {
+  if (!proto) return DSL_ERR_ARG;
+  DSL_PROTO_DISPATCH((dsl::Classes<P>::kSkip))
+}
+
+const char* dsl_event_class_name(const dsl_protocol_desc* proto, int32_t cls) {
+  if (!proto) return nullptr;
+#define DSL_CLASS_NAME (cls >= 0 && cls < dsl::Classes<P>::kSkip ? P::class_name(cls) : nullptr)
+  switch (proto->protocol) {
+    case DSL_PROTO_PINGPONG: { using P = dsl::PingPong; return DSL_CLASS_NAME; }
+    case DSL_PROTO_SIPAXOS: { using P = dsl::SIPaxos; return DSL_CLASS_NAME; }
+    case DSL_PROTO_MULTIPAXOS: { using P = dsl::MultiPaxos; return DSL_CLASS_NAME; }
+    case DSL_PROTO_SYNTHETIC: { using P = dsl::Synthetic; return DSL_CLASS_NAME; }
+    case DSL_PROTO_AMOKV: { using P = dsl::AmoKV; return DSL_CLASS_NAME; }
+    case DSL_PROTO_PB: { using P = dsl::PB; return DSL_CLASS_NAME; }
+    case DSL_PROTO_MINITEST: { using P = dsl::MiniTest; return DSL_CLASS_NAME; }
+    case DSL_PROTO_PINGPONG_IR: { using P = dsl::PingPongIR; return DSL_CLASS_NAME; }
+    case DSL_PROTO_AMOKV_IR: { using P = dsl::AmoKVIR; return DSL_CLASS_NAME; }
+    case DSL_PROTO_MULTIPAXOS_IR: { using P = dsl::MultiPaxosIR; return DSL_CLASS_NAME; }
+    case DSL_PROTO_PB_IR: { using P = dsl::PBIR; return DSL_CLASS_NAME; }
+    default: return nullptr;
+  }
+#undef DSL_CLASS_NAME
+}
+
+int dsl_event_class_is_timer(const dsl_protocol_desc* proto, int32_t cls) {
+  if (!proto) return DSL_ERR_ARG;
+  const int n = dsl_event_class_count(proto);
+  if (n < 0) return n;
+  if (cls < 0 || cls >= n) return DSL_ERR_ARG;
+  DSL_PROTO_DISPATCH((cls >= dsl::Classes<P>::kTimer0 ? 1 : 0))
+}
+
+int dsl_set_event_census(dsl_engine* e, int32_t on) {
+  if (!e) {
+    dsl::set_error("dsl_set_event_census: null engine");
+    return DSL_ERR_ARG;
+  }
+  e->impl->event_census_on = on != 0;
+  e->impl->clear_census();
+  return DSL_OK;
+}
+
+int dsl_event_census(dsl_engine* e, int32_t level, dsl_event_count* cells, int32_t* n_levels) {
+  if (n_levels) *n_levels = 0;
+  if (!e) {
+    dsl::set_error("dsl_event_census: null engine");
+    return DSL_ERR_ARG;
+  }
+  const auto& rows = e->impl->event_census;
+  if (n_levels) *n_levels = (int32_t)rows.size();
+  if (!cells) return DSL_OK;
+  if (level < 0 || level >= (int32_t)rows.size()) {
+    dsl::set_error("dsl_event_census: level " + std::to_string(level) + " of " + std::to_string(rows.size()));
+    return DSL_ERR_ARG;
+  }
+  static_assert(sizeof(dsl_event_count) == 32, "four 64-bit counts");
+  std::memcpy(cells, rows[level].data(), dsl::EngineBase::kEventWords * 8);
+  return DSL_OK;
+}
+
 int dsl_get_initial(dsl_engine* e, uint8_t* packed, size_t len) {
   if (!e || !packed) return DSL_ERR_ARG;
   return e->impl->get_initial(packed, len);

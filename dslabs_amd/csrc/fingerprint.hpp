@@ -128,6 +128,30 @@ __device__ __forceinline__ int table_insert(const Table& t, const Fp& f) {
   return INS_FULL;
 }
 
+// The lookup alone: is f's key in the table as it stands? The walk of table_insert -- the same
+// key, home slot, displacement bound and wrap at the table's end -- with one load per slot and no
+// CAS and no store: the first empty slot answers "absent" (a key lies at or after its home slot
+// with no empty slot in between), a walk past kMaxDisp buckets too (where table_insert answers
+// INS_FULL, the key was never stored). Exact only while no kernel inserts concurrently (a racing
+// insert may or may not be seen); the event census runs it between levels. load_first picks the
+// load as it picks table_insert's: the agent-scope load of the load-first probe, else a plain
+// load (a table within the caches, every slot written by an earlier kernel of the stream).
+__device__ __forceinline__ bool table_contains(const Table& t, const Fp& f) {
+  const uint64_t k0 = table_key0(t, f), home = table_home(t, f), nmask = t.bucket_mask * 8 + 7;
+  uint64_t i = home & nmask;
+  for (int probe = 0; probe < 8 * (kMaxDisp + 1); probe++) {
+    const uint64_t d = ((i >> 3) - (home >> 3)) & t.bucket_mask;
+    if (d > (uint64_t)kMaxDisp) break;
+    const unsigned long long key = (unsigned long long)(k0 | (d << 1));
+    const unsigned long long old =
+        t.load_first ? __hip_atomic_load(t.slots + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : t.slots[i];
+    if (old == 0ull) return false;
+    if (old == key) return true;
+    i = (i + 1) & nmask;
+  }
+  return false;
+}
+
 // The home slot, in the larger table `to` (same b0), of slot word v found at slot index i of
 // `from`: its home bucket in `from` is its bucket minus its displacement; the larger table's
 // extra home bits are the key's stored lo bits.

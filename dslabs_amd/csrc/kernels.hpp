@@ -2020,6 +2020,91 @@ __global__ void __launch_bounds__(kBlock) k_watch_witness(WitnessArgs<P> a, type
   }
 }
 
+// ---- the event census (dsl_set_event_census) ------------------------------------------------------
+// Runs BEFORE a level's k_level, over that level's frontier (in `cur`), with the visited table as
+// it stands then: exactly the states of the depths up to the frontier's. The level's expansion
+// (reexpand_level, every successor taken as new) classifies each applied event into its cell
+// (handler class, destination node) and counts, per cell:
+//   events      live items with a non-null result (STEP_OK or STEP_EXCEPTION), as k_level's
+//               LevelCounters::successors counts them; an event the no-op filters would skip in
+//               k_level runs its handler here and is counted under its real class;
+//   noops       STEP_OK successors equal to their parent (no new record, the same node words);
+//   exceptions  STEP_EXCEPTION;
+//   fresh       the remaining successors whose fingerprint the table does not hold
+//               (table_contains: a lookup, no CAS, no store) -- per event, so two events of the
+//               level that reach one new state are both fresh, and the number depends on neither
+//               arrival order nor buffer and table sizes.
+// The cell is found by a second locate_event on the parent row in LDS (a cold kernel; the
+// visitor's arguments, and with them the other two visitors' code, stay as they are).
+// Counts go to a per-workgroup LDS histogram of kSkip * kNodes * 4 words (<= 480). A protocol's
+// events fall into a few cells (a quarter of C5 Multi-Paxos's are PaxosRequests to the three
+// servers, and a wave's 64 items are consecutive events of a few parents), and lanes adding to
+// one LDS word serialize, so a wave adds per DISTINCT cell: ballots of the three predicates and of
+// the cell, then one pass per distinct cell in which lanes 0-3 each add one popcount to the
+// cell's four words -- one LDS atomic instruction on four distinct addresses per distinct cell
+// (the guides' rule for same-address atomics: reduce in the wave first, one add of the count).
+// At the kernel's exit every non-zero word goes to `out` ([DSL_EVENT_CLASSES][DSL_EVENT_NODES][4]
+// 64-bit words, zeroed on the stream before the launch) with one global atomic.
+// The table, `cur` and `cur_fp` are only read. A kernel of its own: k_level does not move.
+template <class P>
+struct CensusArgs {
+  const uint32_t* cur;
+  const Fp* cur_fp;
+  SegTable segs;             // row ranges of the frontier; pb = parents per wave chunk, chunk0 in those chunks
+  int32_t incremental;
+  Table table;               // read only
+  unsigned long long* out;   // DSL_EVENT_CLASSES * DSL_EVENT_NODES * 4 words
+};
+
+template <class P>
+__global__ void __launch_bounds__(kBlock) k_event_census(CensusArgs<P> a, typename P::Params prm, DevSettings set) {
+  constexpr int NCLS = Classes<P>::kSkip, NCELL = NCLS * P::kNodes;
+  static_assert(NCLS <= DSL_EVENT_CLASSES && P::kNodes <= DSL_EVENT_NODES, "the ABI grid holds every cell");
+  __shared__ uint32_t s_hist[NCELL * 4];  // a workgroup's count of a level is far below 2^32
+  for (int i = threadIdx.x; i < NCELL * 4; i += kBlock) s_hist[i] = 0;
+  __syncthreads();
+  reexpand_level<P>(
+      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, false, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t, int k, const Fp&, Fp f, const NodeView& view) {
+        int cell = -1;
+        bool nop = false, exc = false, fresh = false;
+        if (live && (rc == STEP_OK || rc == STEP_EXCEPTION)) {
+          const uint32_t* w = view.base;  // the parent row in LDS
+          const int e = locate_event<P>(w, prm, set, k);
+          int cls, to;
+          if (e >= 0) {
+            const auto r = Net<P>::at(w, e);
+            cls = P::msg_class(r);
+            to = P::rec_to(r);
+          } else {
+            to = (-1 - e) >> 8;
+            cls = Classes<P>::kTimer0 + TimerClasses<P>::of(to, prm);
+          }
+          if ((unsigned)cls < (unsigned)NCLS && (unsigned)to < (unsigned)P::kNodes) cell = cls * P::kNodes + to;
+          exc = rc == STEP_EXCEPTION;
+          nop = !exc && noop;
+          if (!exc && !nop) fresh = !table_contains(a.table, f);
+        }
+        const unsigned long long m_nop = __ballot(nop), m_exc = __ballot(exc), m_fresh = __ballot(fresh);
+        const int lane = __lane_id();
+        for (unsigned long long rem = __ballot(cell >= 0); rem;) {
+          const int c = (int)rl32((uint32_t)cell, __ffsll((long long)rem) - 1);
+          const unsigned long long m = __ballot(cell == c);
+          rem &= ~m;
+          const unsigned long long mine = lane == 0 ? m : lane == 1 ? (m & m_nop) : lane == 2 ? (m & m_exc) : (m & m_fresh);
+          if (lane < 4 && mine) atomicAdd(&s_hist[c * 4 + lane], (uint32_t)__popcll(mine));
+        }
+      });
+  __syncthreads();
+  for (int i = threadIdx.x; i < NCELL * 4; i += kBlock) {
+    const uint32_t v = s_hist[i];
+    if (v) {
+      const int cell = i >> 2, cls = cell / P::kNodes, to = cell - cls * P::kNodes;
+      atomicAdd(&a.out[(size_t)(cls * DSL_EVENT_NODES + to) * 4 + (i & 3)], (unsigned long long)v);
+    }
+  }
+}
+
 // One hop of many parent chains at once: entry i of `in` holds a row reference (shard << 48 | row)
 // into history level `lev`; this shard answers its own rows with that row's {parent reference,
 // event} in `out` (the next hop's `in`), and leaves the others' entries to their shards' launches.

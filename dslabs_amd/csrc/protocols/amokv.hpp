@@ -49,6 +49,11 @@ struct AmoKV {
   static DSL_HD int m_seq(Rec m) { return (int)((m >> 55) & 3); }
   static DSL_HD uint32_t m_res(Rec m) { return (uint32_t)(m & 0xffffff); }
   static DSL_HD int msg_class(Rec r) { return m_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"Request", "Reply", "ClientTimer"};
+    return kNames[c];
+  }
 
   // values: len:4 | symbols from bit 4; results: type:2 | value << 2
   static DSL_HD uint32_t v_len(uint32_t v) { return v & 15; }

@@ -85,6 +85,11 @@ struct MultiPaxosIR {
   static DSL_HD int rec_from(Rec r) { return (int)((r >> 58) & 7); }
   static DSL_HD int rec_to(Rec r) { return (int)((r >> 55) & 7); }
   static DSL_HD int msg_class(Rec r) { return rec_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"Request", "Reply", "P1a", "P1b", "P2a", "P2b", "Decision", "Heartbeat", "Tick|ClientTimer"};
+    return kNames[c];
+  }
   // node index -> kind: kinds are laid out in declaration order, instances consecutive
   static DSL_HD int num_nodes(const Params& p) { return p.servers + p.clients; }
   static DSL_HD int first_server(const Params& p) { (void)p; return 0; }

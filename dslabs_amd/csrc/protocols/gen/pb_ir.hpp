@@ -83,6 +83,11 @@ struct PBIR {
   static DSL_HD int rec_from(Rec r) { return (int)((r >> 57) & 7); }
   static DSL_HD int rec_to(Rec r) { return (int)((r >> 54) & 7); }
   static DSL_HD int msg_class(Rec r) { return rec_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"Ping", "GetView", "ViewReply", "Request", "Reply", "StateTransfer", "StateTransferAck", "Forward", "ForwardAck", "PingCheckTimer|PingTimer|ClientTimer"};
+    return kNames[c];
+  }
   // node index -> kind: kinds are laid out in declaration order, instances consecutive
   static DSL_HD int num_nodes(const Params& p) { return 1 + p.servers + p.clients; }
   static DSL_HD int first_viewserver(const Params& p) { (void)p; return 0; }

@@ -31,6 +31,11 @@ struct MiniTest {
   static DSL_HD int rec_from(Rec r) { return (int)((r >> 29) & 1); }
   static DSL_HD int rec_to(Rec r) { return (int)((r >> 28) & 1); }
   static DSL_HD int msg_class(Rec r) { return rec_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"Foo", "Bar", "Timer"};
+    return kNames[c];
+  }
 
   static DSL_HD int num_nodes(const Params&) { return 2; }
   template <class O>

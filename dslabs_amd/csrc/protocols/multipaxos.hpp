@@ -73,6 +73,11 @@ struct MultiPaxos {
   // Handler class of a message (< kMsgClasses; timers are class kMsgClasses): k_level groups a chunk's work items
   // by class so that the lanes of a wavefront run the same handler.
   static DSL_HD int msg_class(Rec r) { return m_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"PaxosRequest", "PaxosReply", "P1a", "P1b", "P2a", "P2b", "Decision", "Heartbeat", "TickTimer", "ClientTimer"};
+    return kNames[c];
+  }
   // Timer handler classes: a server's Tick and a client's ClientTimer (nodestate.hpp TimerClasses)
   static constexpr int kTimerClasses = 2;
   static DSL_HD int timer_class(int node, const Params& p) { return node >= p.servers ? 1 : 0; }

@@ -58,6 +58,11 @@ struct PB {
   static DSL_HD int rec_from(Rec m) { return (int)((m >> 57) & 7); }
   static DSL_HD int rec_to(Rec m) { return (int)((m >> 54) & 7); }
   static DSL_HD int msg_class(Rec r) { return m_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"Ping", "GetView", "ViewReply", "Request", "Reply", "StateTransfer", "StateTransferAck", "Forward", "ForwardAck", "PingCheckTimer|PingTimer|ClientTimer"};
+    return kNames[c];
+  }
 
   // views
   static DSL_HD int v_num(int v) { return v & 15; }

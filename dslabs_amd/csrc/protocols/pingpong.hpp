@@ -45,6 +45,11 @@ struct PingPong {
   // Handler class of a message (< kMsgClasses; timers are class kMsgClasses): k_level groups a chunk's work items
   // by class so that the lanes of a wavefront run the same handler.
   static DSL_HD int msg_class(Rec r) { return rec_type(r); }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"PingRequest", "PongReply", "PingTimer"};
+    return kNames[c];
+  }
   static DSL_HD int get(const uint32_t* w, int bit, int width) { return field_get<kNodeWords>(w, bit, width); }
   static DSL_HD void put(uint32_t* w, int bit, int width, int v) { field_put<kNodeWords>(w, bit, width, v); }
   static DSL_HD int ping(const uint32_t* w) { return get(w, 0, 4); }

@@ -52,6 +52,11 @@ struct Synthetic {
   static DSL_HD int rec_from(Rec r) { return (int)((r >> 27) & 7); }
   static DSL_HD int rec_to(Rec r) { return (int)((r >> 24) & 7); }
   static DSL_HD int msg_class(Rec) { return 0; }
+  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.
+  static const char* class_name(int c) {
+    static const char* const kNames[] = {"Poke", "SynthTimer"};
+    return kNames[c];
+  }
 
   static DSL_HD int v_of(const uint32_t* w) { return (int)(w[0] & 0xffff); }
   static DSL_HD int pokes_of(const uint32_t* w) { return (int)((w[0] >> 16) & 3); }

@@ -150,6 +150,13 @@ def generate(p: Protocol, source: str) -> str:
     a(f"  static DSL_HD int rec_from(Rec r) {{ return (int)((r >> {p.from_off}) & {am}); }}")
     a(f"  static DSL_HD int rec_to(Rec r) {{ return (int)((r >> {p.to_off}) & {am}); }}")
     a("  static DSL_HD int msg_class(Rec r) { return rec_type(r); }")
+    # the classes' names (dsl_event_class_name): the message types, then the one timer class
+    cls_names = [m.name for m in p.messages] + ["|".join(t.name for t in p.timers) or "Timer"]
+    a("  // The classes' names (dsl_event_class_name): what the rendered events are called; host only.")
+    a("  static const char* class_name(int c) {")
+    a("    static const char* const kNames[] = {" + ", ".join(f'"{n}"' for n in cls_names) + "};")
+    a("    return kNames[c];")
+    a("  }")
     # node kinds
     a("  // node index -> kind: kinds are laid out in declaration order, instances consecutive")
     cnt = lambda k: str(k.count) if isinstance(k.count, int) else f"p.{k.count}"

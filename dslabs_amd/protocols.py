@@ -8,6 +8,7 @@ MessageEnvelope.java), so traces can be compared with (and replayed on) the orac
 """
 from __future__ import annotations
 
+import ctypes
 from typing import List, Sequence
 
 from . import _lib
@@ -48,6 +49,21 @@ class Protocol:
 
     def render_event(self, e) -> str:
         raise NotImplementedError
+
+    def event_classes(self) -> List[tuple]:
+        """``[(name, is_timer), ...]`` of the protocol's handler classes, messages first: the
+        classes of the event census (SearchSettings.eventCensus). A name is what ``render_event``
+        calls the class's events; a class of several timer types joins their names with ``|``."""
+        cached = self.__dict__.get("_event_classes")
+        if cached is None:
+            lib, d = _lib.load(), self.desc()
+            n = lib.dsl_event_class_count(ctypes.byref(d))
+            if n < 0:
+                raise ValueError(f"dsl_event_class_count: {_lib.STATUS_NAMES.get(n, n)}")
+            cached = [(lib.dsl_event_class_name(ctypes.byref(d), c).decode(),
+                       bool(lib.dsl_event_class_is_timer(ctypes.byref(d), c))) for c in range(n)]
+            self.__dict__["_event_classes"] = cached
+        return list(cached)
 
     def initial_state(self) -> SearchState:
         return SearchState(self)

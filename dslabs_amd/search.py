@@ -17,7 +17,7 @@ from __future__ import annotations
 import ctypes
 import enum
 from dataclasses import dataclass, field
-from typing import List, Optional, Sequence
+from typing import List, NamedTuple, Optional, Sequence
 
 from . import _lib
 from ._lib import check
@@ -446,6 +446,17 @@ class SearchSettings:
         self._watches: List[StatePredicate] = []
         # per watch: the search also returns a witness state of its first hit (dsl_set_watch_witnesses)
         self._witness: List[bool] = []
+        # the event census (dsl_set_event_census): per level, the events applied per handler class
+        # and destination node (SearchResults.eventCensus()); it changes nothing else
+        self._event_census = False
+
+    def eventCensus(self, on: bool = True) -> "SearchSettings":
+        """Counts, per expanded level, the events applied per (handler class, destination node):
+        how many were delivered, led back to their parent, threw, and reached a state not
+        discovered before that level (SearchResults.eventCensus / eventTotals / eventRows). The
+        search itself is unchanged. BFS on one shard."""
+        self._event_census = bool(on)
+        return self
 
     def addWatch(self, p: StatePredicate, witness: bool = False) -> "SearchSettings":
         """Counts, per depth, the newly discovered states in which ``p`` holds, without ending or
@@ -623,7 +634,7 @@ class SearchSettings:
                 tuple(self._link.items()), tuple(self._sender.items()), tuple(self._receiver.items()),
                 tuple(self._timers_active.items()), tuple(self._invariants), tuple(self._goals), tuple(self._prunes),
                 self.table_log2_slots, self.max_frontier_states, self.memory_budget_bytes, self.do_checks,
-                self.check_sample, self.max_terminals, tuple(self._watches), tuple(self._witness))
+                self.check_sample, self.max_terminals, tuple(self._watches), tuple(self._witness), self._event_census)
 
     def _encode(self, state: "SearchState") -> _lib.dsl_settings:
         """The C ABI form (dsl_settings); the same object again while nothing it reads changed,
@@ -774,6 +785,19 @@ class SearchState:
         return list(self.protocol.addresses)
 
 
+class EventCount(NamedTuple):
+    """One cell of the event census: the events of one handler class delivered to one node."""
+    events: int
+    noops: int
+    exceptions: int
+    fresh: int
+
+    @property
+    def revisits(self) -> int:
+        """Events that reached a state discovered at the parents' depth or before."""
+        return self.events - self.noops - self.exceptions - self.fresh
+
+
 class SearchResults:
     def __init__(self, end, states, per_depth, initial_depth, max_depth, terminal: Optional[SearchState],
                  predicate: Optional[PredicateResult], elapsed_s: float, successors: int):
@@ -793,6 +817,9 @@ class SearchResults:
         self._watch_counts: List[List[int]] = []
         self._watch_totals: List[int] = []
         self._witnesses: List[Optional[SearchState]] = []
+        self._event_rows: list = []       # [level][cls][to] = (events, noops, exceptions, fresh)
+        self._event_classes: list = []    # [(name, is_timer)] of the protocol
+        self._event_addresses: list = []
 
     def endCondition(self) -> EndCondition:
         return self._end
@@ -872,6 +899,35 @@ class SearchResults:
         if not 0 <= i < n:
             raise ValueError(f"watchWitness: watch {i} of {n}")
         return self._witnesses[i] if i < len(self._witnesses) else None
+
+    # the event census (SearchSettings.eventCensus) ----------------------------------------------
+    def eventRows(self) -> list:
+        """The raw census: ``rows[i][cls][to] = (events, noops, exceptions, fresh)`` of the events
+        applied to the states of depth ``initial_depth + i``, one row per level whose expansion
+        completed; ``cls`` indexes ``Protocol.event_classes()``, ``to`` the protocol's addresses.
+        Empty without the census, and after a DFS or a replay."""
+        return [[[tuple(v) for v in c] for c in row] for row in self._event_rows]
+
+    def eventCensus(self) -> List[dict]:
+        """One dict per row, ``{(class_name, address): EventCount}``, of the cells with events."""
+        out = []
+        for row in self._event_rows:
+            d = {}
+            for c, cells in enumerate(row):
+                for t, v in enumerate(cells):
+                    if v[0] > 0:
+                        d[(self._event_classes[c][0], self._event_addresses[t])] = EventCount(*v)
+            out.append(d)
+        return out
+
+    def eventTotals(self) -> dict:
+        """``eventCensus()`` summed over the rows."""
+        tot: dict = {}
+        for d in self.eventCensus():
+            for k, v in d.items():
+                o = tot.get(k)
+                tot[k] = v if o is None else EventCount(*(a + b for a, b in zip(o, v)))
+        return tot
 
     def statesPerSecond(self) -> float:
         return self.states / self.elapsed_s if self.elapsed_s > 0 else float("inf")
@@ -963,6 +1019,10 @@ class Engine:
         if settings._watches and settings._witness_mask() != getattr(self, "_set_witness_mask", 0):
             check(lib.dsl_set_watch_witnesses(self.handle, settings._witness_mask()), "dsl_set_watch_witnesses")
             self._set_witness_mask = settings._witness_mask()
+        # the event census: told only when it differs from what the engine holds
+        if settings._event_census != getattr(self, "_set_event_census", False):
+            check(lib.dsl_set_event_census(self.handle, int(settings._event_census)), "dsl_set_event_census")
+            self._set_event_census = settings._event_census
         if state.packed is not None:
             buf = (ctypes.c_uint8 * len(state.packed)).from_buffer_copy(state.packed)
             check(lib.dsl_set_initial(self.handle, buf, len(state.packed), state.depth()), "dsl_set_initial")
@@ -987,6 +1047,18 @@ class Engine:
                                             ctypes.byref(total)), "dsl_watch_counts")
             res._watch_counts.append([buf[i] for i in range(min(n.value, len(res.per_depth)))])
             res._watch_totals.append(total.value)
+        if settings._event_census:  # the event census of this run (dsl_event_census)
+            n = ctypes.c_int32(0)
+            check(self.lib.dsl_event_census(self.handle, 0, None, ctypes.byref(n)), "dsl_event_census")
+            ncls, nn = len(self.protocol.event_classes()), len(self.protocol.addresses)
+            cells = (_lib.dsl_event_count * (_lib.DSL_EVENT_CLASSES * _lib.DSL_EVENT_NODES))()
+            for lev in range(n.value):
+                check(self.lib.dsl_event_census(self.handle, lev, cells, None), "dsl_event_census")
+                res._event_rows.append([[(x.events, x.noops, x.exceptions, x.fresh)
+                                         for x in cells[c * _lib.DSL_EVENT_NODES:c * _lib.DSL_EVENT_NODES + nn]]
+                                        for c in range(ncls)])
+            res._event_classes = self.protocol.event_classes()
+            res._event_addresses = list(self.protocol.addresses)
         if any(settings._witness):  # the witnesses of this run (dsl_watch_witness)
             base = state.trace() if state.packed is not None else []
             nb = self.state_bytes()

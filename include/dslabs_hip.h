@@ -46,7 +46,10 @@ extern "C" {
                             DSL_ERR_UNKNOWN_PREDICATE.
                             Still 6 with dsl_set_watches / dsl_watch_counts: two entry points are
                             added, no struct changes; a caller that never names them runs as before.
-                            Still 6 with dsl_set_watch_witnesses / dsl_watch_witness: the same again */
+                            Still 6 with dsl_set_watch_witnesses / dsl_watch_witness: the same again
+                            Still 6 with dsl_set_event_census / dsl_event_census / dsl_event_class_count /
+                            _name / _is_timer: five entry points and dsl_event_count are added;
+                            dsl_settings, dsl_result and dsl_stats keep their bytes */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -417,6 +420,50 @@ int dsl_set_watch_witnesses(dsl_engine* e, uint32_t mask);
    packed state's size. A null engine or a watch index outside the watches set is DSL_ERR_ARG. */
 int dsl_watch_witness(dsl_engine* e, int32_t watch, int32_t* depth, dsl_event* trace, int32_t cap,
                       int32_t* trace_len, uint8_t* state, size_t len);
+
+/* The event census: transitions, where the watches count states. Opt-in, for dsl_run on one shard.
+ * For every level whose expansion completed -- a queued level, a do_checks level and the level that
+ * ends the search with a terminal included; not a level cut short by max_time_ms, and not the
+ * maxDepth frontier, which is not expanded -- row i holds one cell per (handler class, destination
+ * node) with four counts of the events applied to the states of depth initial_depth + i:
+ *   events      enabled events delivered with a non-null result, exactly as dsl_result.successors
+ *               counts them: in a search in which no level was cut short, the events of all rows
+ *               and cells sum to `successors`;
+ *   noops       successors equal to their parent (no new record, the same node words);
+ *   exceptions  events whose handler threw;
+ *   fresh       successors that are neither, whose state had not been discovered at any depth
+ *               <= initial_depth + i: a read-only lookup in the visited table as it stands before
+ *               the level inserts anything. Counted per event -- two events of one level that reach
+ *               the same new state are both fresh -- so the number depends on no arrival order,
+ *               buffer size, table size or restart. events - noops - exceptions - fresh is the
+ *               cell's revisit count.
+ * A message's class is its handler class (dsl_event_class_name) and its node the destination; a
+ * timer's class is its node's timer class and its node the timer's node. An event whose handler the
+ * engine proves idle and skips in a plain search is counted under its real class. Classes are
+ * [0, dsl_event_class_count), nodes [0, the protocol's nodes); the other cells of the
+ * DSL_EVENT_CLASSES x DSL_EVENT_NODES grid are zero. The search itself is the same with or without
+ * the census: states, per_depth, successors, end condition, terminals, traces, check counts, watch
+ * census and witnesses (the levels run one by one instead of queued on the device, as with
+ * do_checks). A search restarted for table growth counts from zero. dsl_run with the census on and
+ * virtual_shards > 1 or world_size > 1 returns DSL_ERR_ARG before any collective. dsl_run_dfs,
+ * dsl_replay and dsl_human_readable_trace report no rows. */
+#define DSL_EVENT_CLASSES 15
+#define DSL_EVENT_NODES 8
+typedef struct { uint64_t events, noops, exceptions, fresh; } dsl_event_count;
+/* The protocol's handler classes: their number, a class's name (static storage; the message or
+   timer names dsl_human_readable_trace prints, joined with '|' where a class holds several; NULL
+   outside [0, count) or for an unknown protocol) and whether it is a timer class (1 / 0; negative:
+   error). Message classes come first. */
+int dsl_event_class_count(const dsl_protocol_desc* proto);
+const char* dsl_event_class_name(const dsl_protocol_desc* proto, int32_t cls);
+int dsl_event_class_is_timer(const dsl_protocol_desc* proto, int32_t cls);
+/* Turns the census on (non-zero) or off. Kept across dsl_set_settings, like the watches. */
+int dsl_set_event_census(dsl_engine* e, int32_t on);
+/* Row `level` of the last dsl_run: DSL_EVENT_CLASSES * DSL_EVENT_NODES cells, class-major, written
+   to `cells` unless it is NULL; *n_levels = the rows there are (0 after any other call, or without
+   the census). A null engine, or a level outside [0, n_levels) with non-null cells, is DSL_ERR_ARG
+   (named in dsl_last_error). */
+int dsl_event_census(dsl_engine* e, int32_t level, dsl_event_count* cells, int32_t* n_levels);
 
 /* Random depth-first search (Search.dfs / RandomDFS, Search.java:397-402, :507-583): `probes`
  * independent random walks run concurrently on the device (one per lane), each restarted from

@@ -144,6 +144,12 @@ struct BfsEngine : EngineBase {
     uint32_t* next = nullptr;
     Fp* cur_fp = nullptr;
     Fp* next_fp = nullptr;
+    // sleep sets (nodestate.hpp): each row's creator word and new-record mask, sized and swapped
+    // with the fingerprints (grow_fp)
+    uint32_t* cur_cw = nullptr;
+    uint32_t* next_cw = nullptr;
+    uint64_t* cur_cm = nullptr;
+    uint64_t* next_cm = nullptr;
     uint64_t cur_cap = 0, next_cap = 0, curfp_cap = 0, nextfp_cap = 0;
     // history: per BFS level of the search (index = depth - initial depth), parent pointer and
     // event of every row of that level's frontier; one buffer pair per level, kept across
@@ -356,7 +362,7 @@ struct BfsEngine : EngineBase {
       void* ptrs[] = {s.table,     s.cur,      s.next,   s.cur_fp, s.next_fp, s.terms,  s.rc,
                       s.out_key,   s.in_fp,    s.rep_out, s.rep_in, s.spill, s.ctrbuf,
                       s.find_ctr,  s.rspill,   s.out2,    s.rep2,   s.out_item, s.out2_item, s.newl, s.nl_ctr,
-                      s.out_pk,    s.in_pk};
+                      s.out_pk,    s.in_pk,    s.cur_cw,  s.next_cw, s.cur_cm, s.next_cm};
       for (void* q : ptrs) (void)hipFree(q);
       for (auto* q : s.hpar) (void)hipFree(q);
       for (auto* q : s.hev) (void)hipFree(q);
@@ -538,7 +544,16 @@ struct BfsEngine : EngineBase {
     std::swap(S.cur_cap, S.next_cap);
     std::swap(S.cur_fp, S.next_fp);
     std::swap(S.curfp_cap, S.nextfp_cap);
+    std::swap(S.cur_cw, S.next_cw);
+    std::swap(S.cur_cm, S.next_cm);
     S.flip = !S.flip;
+  }
+  // Sleep sets for the search about to run (decided once, in begin_search): the protocol has them,
+  // one shard, every record deliverable, no prune -- a pruned state is not expanded, and the rule
+  // needs every state of a level expanded -- and DSL_NO_SLEEP unset (the A/B's and the tests' switch).
+  bool sleep_on = false;
+  bool sleep_allowed() const {
+    return sleep_sets_apply<P>(dset) && W == 1 && sh.size() == 1 && !getenv("DSL_NO_SLEEP");
   }
   // What every k_level launch over shard S sets alike: the frontier in and out (flip: a queue's
   // odd levels run next -> cur) with history level `lev` for the successors' parents and events,
@@ -556,7 +571,14 @@ struct BfsEngine : EngineBase {
     a.term_cap = find ? 1 : term_cap;
     a.W = W;
     a.me = S.gid;
-    if (find) return a;
+    if (find) return a;  // (find mode expands every event: no creator is read)
+    if constexpr (SleepSets<P>::value) {
+      a.cur_cw = flip ? S.next_cw : S.cur_cw;
+      a.cur_cm = flip ? S.next_cm : S.cur_cm;
+      a.next_cw = flip ? S.cur_cw : S.next_cw;
+      a.next_cm = flip ? S.cur_cm : S.next_cm;
+      a.sleep = sleep_on ? 1 : 0;
+    }
     a.table = tbl;
     a.table.slots = S.table;
     a.spill = S.spill;
@@ -567,7 +589,7 @@ struct BfsEngine : EngineBase {
   }
 
   template <class T>
-  int grow(T** ptr, uint64_t* cap, uint64_t need, bool keep, uint64_t keep_elems) {
+  int grow(T** ptr, uint64_t* cap, uint64_t need, bool keep, uint64_t keep_elems, bool sync = true) {
     if (need <= *cap && *ptr) return DSL_OK;
     const uint64_t ncap = std::max<uint64_t>(std::max<uint64_t>(need, *cap + *cap / 2), 1024);
     T* np = nullptr;
@@ -578,11 +600,24 @@ struct BfsEngine : EngineBase {
     DSL_HIP(hipMalloc(&np, ncap * sizeof(T)));
     if (keep && *ptr && keep_elems)
       DSL_HIP(hipMemcpyAsync(np, *ptr, keep_elems * sizeof(T), hipMemcpyDeviceToDevice, stream));
-    DSL_TRY(hsync());
+    if (sync) DSL_TRY(hsync());  // (else hipFree, which waits for the device, drains the copy)
     (void)hipFree(*ptr);
     *ptr = np;
     *cap = ncap;
     return DSL_OK;
+  }
+  // A frontier's fingerprints with its creator records (sleep sets): three arrays of one capacity,
+  // grown by the one rule of grow(). The creator arrays go first and without a host round trip of
+  // their own (sync = false): the fingerprints' grow reallocates whenever they do, and its round
+  // trip is the search's one for this growth.
+  int grow_fp(Shard& S, bool next, uint64_t need, bool keep, uint64_t keep_elems) {
+    uint64_t* cap = next ? &S.nextfp_cap : &S.curfp_cap;
+    if constexpr (SleepSets<P>::value) {
+      uint64_t c1 = *cap, c2 = *cap;
+      DSL_TRY(grow(next ? &S.next_cw : &S.cur_cw, &c1, need, keep, keep_elems, false));
+      DSL_TRY(grow(next ? &S.next_cm : &S.cur_cm, &c2, need, keep, keep_elems, false));
+    }
+    return grow(next ? &S.next_fp : &S.cur_fp, cap, need, keep, keep_elems);
   }
   int grow_rows(uint32_t** ptr, uint64_t* cap, uint64_t rows, bool keep, uint64_t keep_rows) {
     uint64_t cw = *cap * NW;
@@ -681,7 +716,8 @@ struct BfsEngine : EngineBase {
   // the LDS budget of the staged rows.
   // LDS per staged parent: its row, fingerprint, node hashes (kernels.hpp k_level step 2) and offset
   // (+16 per chunk: LdsRow::image rounds the padded row image up to 16 bytes)
-  static constexpr size_t kRowLds = (size_t)LdsRow<P>::kStride * 4 + sizeof(Fp) * (1 + P::kNodes) + 4;
+  // (+ the creator record of a protocol with sleep sets whose rows have no padding for it)
+  static constexpr size_t kRowLds = (size_t)LdsRow<P>::kStride * 4 + sizeof(Fp) * (1 + P::kNodes) + 4 + LdsRow<P>::kCrLds;
   int pb_max() const {
     const int lds_max = (int)(kRowsLdsBytes / kRowLds);
     const int want = (int)((3 * kLevelBlock * 16 + avg_events_x16 - 1) / std::max<uint64_t>(avg_events_x16, 1));
@@ -762,9 +798,9 @@ struct BfsEngine : EngineBase {
     uint64_t used = 0;  // rows of the current frontier that must be kept
     for (size_t q = 0; q < S.seg_cnt.size(); q++) used = std::max(used, S.seg_base[q] + S.seg_cnt[q]);
     DSL_TRY(grow_rows(&S.cur, &S.cur_cap, std::max(span, used), true, used));
-    DSL_TRY(grow(&S.cur_fp, &S.curfp_cap, std::max(span, used), true, used));
+    DSL_TRY(grow_fp(S, false, std::max(span, used), true, used));
     DSL_TRY(grow_rows(&S.next, &S.next_cap, span, false, 0));
-    DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, span, false, 0));
+    DSL_TRY(grow_fp(S, true, span, false, 0));
     const size_t lev0 = S.level_size.size();  // the history level of the first queued level's rows
     for (int j = 0; j < nq; j++) DSL_TRY(hist_grow(S, lev0 + j, span, 0));
     DSL_TRY(grow(&S.spill, &S.spill_cap, wlimit, false, 0));
@@ -1313,7 +1349,7 @@ struct BfsEngine : EngineBase {
     DSL_TRY(grow_x(&S.newl, &S.newl_cap, std::max<uint64_t>(mat_rows, 1)));
     const uint64_t rows = S.seg_span + S.uns_room + S.mat_room;
     DSL_TRY(grow_rows(&S.next, &S.next_cap, rows, false, 0));
-    DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, rows, false, 0));
+    DSL_TRY(grow_fp(S, true, rows, false, 0));
     DSL_TRY(hist_grow(S, S.level_size.size(), rows, 0));
     if (!S.nl_ctr) DSL_HIP(hipMalloc(&S.nl_ctr, (2 + kMaxShards) * 8));
     return DSL_OK;
@@ -1559,6 +1595,7 @@ struct BfsEngine : EngineBase {
     ma.incremental = depth > init_depth ? 1 : 0;
     ma.next = S.next;
     ma.next_fp = S.next_fp;
+    ma.next_cw = S.next_cw;
     ma.next_parent = S.hpar[lv];
     ma.next_event = S.hev[lv];
     ma.next_base = S.seg_span + S.uns_room;
@@ -1635,7 +1672,7 @@ struct BfsEngine : EngineBase {
       const uint64_t need = used + more + ovf;
       if (need > used) {
         DSL_TRY(grow_rows(&S.next, &S.next_cap, need, true, used));
-        DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, need, true, used));
+        DSL_TRY(grow_fp(S, true, need, true, used));
         DSL_TRY(hist_grow(S, lv, need, used));
       }
       if (!last) S.mat_room += more;
@@ -1716,7 +1753,7 @@ struct BfsEngine : EngineBase {
       const int blocks = (int)std::min<uint64_t>((S.ovf_cnt + kBlock - 1) / kBlock, 8192);
       hipLaunchKernelGGL(k_unspill<P>, dim3(blocks), dim3(kBlock), 0, stream, (const uint64_t*)(S.spill + S.uns_room),
                          S.ovf_cnt, (const uint32_t*)S.cur, (const Fp*)S.cur_fp, S.next, S.next_fp, S.hpar[lv], S.hev[lv],
-                         S.ovf_base, S.gid, S.ctr, prm, dset, nullptr);
+                         S.ovf_base, S.gid, S.ctr, prm, dset, nullptr, S.next_cw);
       DSL_HIP(hipGetLastError());
       extra[l] = S.ovf_cnt;
     }
@@ -1965,8 +2002,8 @@ struct BfsEngine : EngineBase {
       S.seg_cnt.clear();
       DSL_TRY(grow_rows(&S.cur, &S.cur_cap, 1024, false, 0));
       DSL_TRY(grow_rows(&S.next, &S.next_cap, 1024, false, 0));
-      DSL_TRY(grow(&S.cur_fp, &S.curfp_cap, 1024, false, 0));
-      DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, 1024, false, 0));
+      DSL_TRY(grow_fp(S, false, 1024, false, 0));
+      DSL_TRY(grow_fp(S, true, 1024, false, 0));
       // every search starts with the same buffer of each pair as `cur`: the two then take the
       // same roles level by level in every search, so a repeated search reallocates nothing
       if (S.flip) swap_frontier(S);
@@ -1992,6 +2029,7 @@ struct BfsEngine : EngineBase {
     // ... and the event census runs its pass before every level's k_level, on the table as it
     // stands then
     r.use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE && !event_census_on;
+    sleep_on = sleep_allowed();
     if (event_census_on) {
       if (!ev_dev) DSL_HIP(hipMalloc(&ev_dev, kEventWords * 8));
       if (!ev_host) DSL_HIP(hipHostMalloc(&ev_host, kEventWords * 8));
@@ -2067,6 +2105,7 @@ struct BfsEngine : EngineBase {
       sa.key = (unsigned long long)table_key0(tbl, init_fp);
       sa.cur = S.cur;
       sa.cur_fp = S.cur_fp;
+      sa.cur_cw = S.cur_cw;
       sa.fp = init_fp;
       std::memcpy(sa.init, init.w, NW * 4);
       const int sgrid = sa.clean ? 1 : (int)std::min<uint64_t>(4096, std::max<uint64_t>(1, sa.n_table / kBlock));
@@ -2223,7 +2262,7 @@ struct BfsEngine : EngineBase {
       S.segcap = (want + S.nseg - 1) / S.nseg + 1;
       const uint64_t rows = S.segcap * S.nseg;
       DSL_TRY(grow_rows(&S.next, &S.next_cap, rows, false, 0));
-      DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, rows, false, 0));
+      DSL_TRY(grow_fp(S, true, rows, false, 0));
       DSL_TRY(hist_grow(S, S.level_size.size(), rows, 0));
       DSL_TRY(grow(&S.spill, &S.spill_cap, std::max<uint64_t>(S.work, 1), false, 0));
     }
@@ -2375,12 +2414,12 @@ struct BfsEngine : EngineBase {
       const uint64_t keep = o.span[l], need = keep + ns;
       const size_t lv = S.level_size.size();
       DSL_TRY(grow_rows(&S.next, &S.next_cap, need, true, keep));
-      DSL_TRY(grow(&S.next_fp, &S.nextfp_cap, need, true, keep));
+      DSL_TRY(grow_fp(S, true, need, true, keep));
       DSL_TRY(hist_grow(S, lv, need, keep));
       const int blocks = (int)std::min<uint64_t>((ns + kBlock - 1) / kBlock, 256ull * 32);
       LevelCounters* uctr = p.queued ? reinterpret_cast<LevelCounters*>(qctr + (size_t)q_pos * kCtrSet) : S.ctr;
       hipLaunchKernelGGL(k_unspill<P>, dim3(blocks), dim3(kBlock), 0, stream, S.spill, ns, S.cur, S.cur_fp, S.next,
-                         S.next_fp, S.hpar[lv], S.hev[lv], keep, S.gid, uctr, prm, dset, nullptr);
+                         S.next_fp, S.hpar[lv], S.hev[lv], keep, S.gid, uctr, prm, dset, nullptr, S.next_cw);
       o.nbase[l].push_back(keep);
       o.ncnt[l].push_back(ns);
       o.span[l] = need;

@@ -61,6 +61,10 @@ struct LdsRow {
   static constexpr int kStride = kWords + kPad;
   // dwords of a chunk's row image (rounded to 16 B, so the fingerprints after it stay aligned)
   static constexpr int image(int pb) { return (pb * kStride + 3) / 4 * 4; }
+  // a staged parent's creator record (3 words, sleep sets): in its row's padding, else in an array
+  // of its own behind the chunk's offsets (kCrLds bytes per parent)
+  static constexpr bool kCrInPad = kPad >= 3;
+  static constexpr int kCrLds = (SleepSets<P>::value && !kCrInPad) ? 12 : 0;
 };
 constexpr int kMaxSegs = kSegs + 2;
 constexpr int kSegStride = 16;  // u64 words between segment counters (one 128-byte line each)
@@ -280,9 +284,14 @@ __device__ __forceinline__ void block_flush(unsigned long long* red, unsigned lo
 // nw_lds (k_level): the changed nodes' words already in LDS, kNodeWords per lane of the workgroup
 // (s_nodew; `lane0` = the wave's first lane there): a header word then comes from one LDS read
 // instead of kNodeWords readlanes and selects per row.
-template <class P, int STRIDE = Layout<P>::kWords>
+// MASK (k_level with sleep sets; at most 64 records): when `want_mask` (wave-uniform), the lane that
+// owns a row also gets, in *new_mask, the mask of the merged array's slots that its kept sends
+// took -- the ranks this emission gave them, which are creator_record's slots (nodestate.hpp): one
+// readlane per kept send instead of a lower bound per send in the owning lane.
+template <class P, int STRIDE = Layout<P>::kWords, bool MASK = false>
 __device__ __forceinline__ bool wave_emit(bool active, const uint32_t* base, uint64_t pidx, const Delta<P>& d,
-                                          uint32_t* dst, const uint32_t* nw_lds = nullptr) {
+                                          uint32_t* dst, const uint32_t* nw_lds = nullptr, bool want_mask = false,
+                                          uint64_t* new_mask = nullptr) {
   bool collision = false;
   using L = Layout<P>;
   using Rec = typename P::Rec;
@@ -374,6 +383,15 @@ __device__ __forceinline__ bool wave_emit(bool active, const uint32_t* base, uin
           }
           q++;
         }
+      }
+    }
+    if constexpr (MASK) {
+      static_assert(TR == 1, "the new-record mask is one 64-bit word");
+      if (want_mask) {  // lanes [n, n + m) hold the kept sends, rk[0] their slots
+        const int n0 = __builtin_amdgcn_readfirstlane(n);
+        unsigned long long nm = 0;
+        for (int s = n0; s < n0 + m; s++) nm |= 1ull << (rl32((uint32_t)rk[0], s & 63) & 63u);
+        if (lane == src) *new_mask = nm;
       }
     }
     // only the row's n + m records are stored: the free slots after them (and the padding) keep
@@ -473,8 +491,23 @@ __device__ __forceinline__ bool lane_emit(bool active, const uint32_t* pw, const
 __device__ __forceinline__ uint64_t item_parent(uint64_t item) { return item >> 20; }
 __device__ __forceinline__ int item_event(uint64_t item) { return (int)(item & 0xfffff); }
 
+// The frontier's creator records (nodestate.hpp: sleep sets), beside the fingerprints: 12 bytes per
+// state, ping-ponged with the row buffers. A base of LevelArgs that is empty for a protocol
+// without sleep sets, whose kernel arguments keep their layout.
+template <bool ON>
+struct SleepArgs {};
+template <>
+struct SleepArgs<true> {
+  const uint32_t* cur_cw;    // creator words of the frontier rows (0: none)
+  const uint64_t* cur_cm;    // ... and their new-record masks
+  uint32_t* next_cw;         // the same for the next frontier
+  uint64_t* next_cm;
+  int32_t sleep;             // the rule is on for this search (BfsEngine::sleep_on)
+  int32_t sleep_pad;
+};
+
 template <class P>
-struct LevelArgs {
+struct LevelArgs : SleepArgs<SleepSets<P>::value> {
   const uint32_t* cur;       // frontier rows of kWords (row ranges in `segs`)
   const Fp* cur_fp;
   SegTable segs;
@@ -688,6 +721,10 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
   Fp* fps = reinterpret_cast<Fp*>(rows + LdsRow<P>::image(a.PB));  // a.PB
   Fp* nh = fps + a.PB;                                       // a.PB * kNodes: the parents' node hashes
   int* off = reinterpret_cast<int*>(nh + a.PB * P::kNodes);  // a.PB + 1
+  // sleep sets: never in a sharded level, and compiled out for a protocol without them
+  constexpr bool SLEEP = SleepSets<P>::value && !ROUTE;
+  [[maybe_unused]] uint32_t* crs = reinterpret_cast<uint32_t*>(off + a.PB + 1);  // 3 a.PB (unless in the rows' padding)
+  [[maybe_unused]] auto creator_lds = [&](int j) { return LdsRow<P>::kCrInPad ? rows + j * SP + NW : crs + 3 * j; };
   __shared__ SegTable s_segs;
   __shared__ uint32_t s_nodew[kLevelBlock * P::kNodeWords];
   __shared__ typename P::Rec s_sends[NetPreds<P>::value ? kLevelBlock * P::kMaxSends : 1];
@@ -789,7 +826,25 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
     else
       stage_rows_dma<NW, SP>(reinterpret_cast<const uint4*>(a.cur + p0 * NW), rows, pb);
     stage_lds(reinterpret_cast<const uint4*>(a.cur_fp + p0), reinterpret_cast<uint4*>(fps), pb);
-    __builtin_amdgcn_s_waitcnt(0);
+    if constexpr (SLEEP) {
+      // the parents' creator records, loaded beside the DMA (the same wait covers them); find mode
+      // and a search with the rule off read none, so nothing sleeps
+      uint32_t pcw = 0;
+      uint64_t pcm = 0;
+      if (a.sleep && tid < pb) {
+        pcw = a.cur_cw[p0 + tid];
+        pcm = a.cur_cm[p0 + tid];
+      }
+      __builtin_amdgcn_s_waitcnt(0);
+      if (tid < pb) {
+        uint32_t* cr = creator_lds(tid);
+        cr[0] = pcw;
+        cr[1] = (uint32_t)pcm;
+        cr[2] = (uint32_t)(pcm >> 32);
+      }
+    } else {
+      __builtin_amdgcn_s_waitcnt(0);
+    }
     __syncthreads();
     PH_MARK(9);  // staging (LDS-DMA + wait + barrier)
     // 2. every parent's node hashes, once per parent instead of once per successor (the old-node
@@ -869,10 +924,19 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
           if (set.all_deliver) {  // event k < size is record k (SearchState.events: messages first)
             const int mhi = min(hi, e0 + (int)Net<P>::size(w));
             const int nn = P::num_nodes(prm);
+            [[maybe_unused]] uint32_t cw = 0;
+            [[maybe_unused]] uint64_t cm = 0;
+            if constexpr (SLEEP) {
+              const uint32_t* cr = creator_lds(j);
+              cw = cr[0];
+              cm = (uint64_t)cr[1] | ((uint64_t)cr[2] << 32);
+            }
             for (; q < mhi; q += tpp) {
               const auto r = Net<P>::at(w, q - e0);
               const int i = P::rec_to(r);
-              const bool skip = i < nn && NoopFilter<P>::msg(i < nn ? i : 0, w, r, prm);
+              bool skip = i < nn && NoopFilter<P>::msg(i < nn ? i : 0, w, r, prm);
+              // a sleeping event sorts into the skip class: counted, never run (nodestate.hpp)
+              if constexpr (SLEEP) skip |= sleeping_rec<typename P::Rec>(cw, cm, q - e0, r, i, nn);
               const int cls = skip ? Classes<P>::kSkip : P::msg_class(r);
               s_par[q - w0] = (uint8_t)j;
               s_cls[q - w0] = (uint8_t)cls;
@@ -1122,8 +1186,25 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
             c_next_work += (uint32_t)delta_event_count<P>(w, off[j + 1] - off[j], d, prm, set);
           }
           bool coll;
+          [[maybe_unused]] uint64_t ncm = 0;  // sleep sets: the slots of this lane's row that its kept sends take
+          [[maybe_unused]] bool want_mask = false;
+          if constexpr (SLEEP) want_mask = a.sleep != 0;
           if constexpr (LaneEmit<P>::value) coll = lane_emit<P>(fits, rows + j * SP, d, a.next + idx * NW);
-          else coll = wave_emit<P, SP>(fits, rows, (uint64_t)j, d, a.next + idx * NW, s_nodew + (tid - lane) * P::kNodeWords);
+          else coll = wave_emit<P, SP, SLEEP>(fits, rows, (uint64_t)j, d, a.next + idx * NW,
+                                              s_nodew + (tid - lane) * P::kNodeWords, want_mask, &ncm);
+          if constexpr (SLEEP) {
+            // the successor's creator record (every record is deliverable: event k < size is record k)
+            if (a.sleep && fits) {
+              const uint32_t* w = rows + j * SP;
+              const int e = k < Net<P>::size(w) ? k : -1;
+              if constexpr (LaneEmit<P>::value) {
+                uint32_t ncw;
+                creator_record<P>(w, e, d, &ncw, &ncm);
+              }
+              a.next_cw[idx] = creator_word<P>(w, e, d.node);
+              a.next_cm[idx] = ncm;
+            }
+          }
           if (coll && lane == 0)
             atomicAdd(&a.ctr->err_overflow, 1ull);  // two equal kept sends (see wave_emit)
           PH_MARK(6);  // history + row emission
@@ -1218,7 +1299,8 @@ __global__ void __launch_bounds__(kBlock) k_unspill(const uint64_t* items, uint6
                                                     const Fp* cur_fp, uint32_t* next, Fp* next_fp,
                                                     uint64_t* next_parent, uint32_t* next_event, uint64_t base_idx,
                                                     int32_t me, LevelCounters* ctr, typename P::Params prm,
-                                                    DevSettings set, const unsigned long long* n_dev = nullptr) {
+                                                    DevSettings set, const unsigned long long* n_dev = nullptr,
+                                                    uint32_t* next_cw = nullptr) {
   constexpr int NW = Layout<P>::kWords;
   __shared__ unsigned long long s_red[kBlock / 64];
   unsigned long long c_next_work = 0;
@@ -1243,6 +1325,7 @@ __global__ void __launch_bounds__(kBlock) k_unspill(const uint64_t* items, uint6
       next_fp[idx] = delta_fingerprint<P>(w, cur_fp[parent], d);
       next_parent[idx] = ((uint64_t)me << 48) | parent;
       next_event[idx] = (uint32_t)k;
+      if (next_cw) next_cw[idx] = 0u;  // sleep sets: this path records no creator
       ne = (unsigned long long)delta_event_count<P>(w, count_events<P>(w, prm, set), d, prm, set);
     }
     if (wave_emit<P>(ok, cur, parent, d, next + (base_idx + i) * NW) && __lane_id() == 0)
@@ -1271,6 +1354,7 @@ struct SetupArgs {
   unsigned long long key;
   uint32_t* cur;
   Fp* cur_fp;
+  uint32_t* cur_cw;   // sleep sets: the seed has no creator (null: the protocol has none)
   Fp fp;
   uint32_t init[Layout<P>::kWords];
 };
@@ -1296,6 +1380,7 @@ __global__ void __launch_bounds__(kBlock) k_setup(SetupArgs<P> a) {
     if (a.seed) {
       for (int i = threadIdx.x; i < Layout<P>::kWords; i += blockDim.x) a.cur[i] = a.init[i];
       if (threadIdx.x == 0) *a.cur_fp = a.fp;
+      if (threadIdx.x == 0 && a.cur_cw) *a.cur_cw = 0u;
     }
   }
 }
@@ -1612,6 +1697,7 @@ struct MaterializeArgs {
   TerminalRec* terms;
   uint32_t term_cap;
   int32_t per_fixed;                 // states per wave (<= the LDS rows per wave), 0: from the list size
+  uint32_t* next_cw;                 // sleep sets: the appended rows have no creator (null: no array)
 };
 
 // States per wave at most in k_materialize: a wave stages its states' parent rows in LDS (8 KiB
@@ -1757,6 +1843,7 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
     const uint64_t idx = a.seg_ctr ? (uint64_t)seg * a.segcap + li : a.next_base + li;
     if (fits) {
       a.next_fp[idx] = f;
+      if (a.next_cw) a.next_cw[idx] = 0u;  // this path records no creator
       a.next_parent[idx] = ((uint64_t)a.me << 48) | parent;
       a.next_event[idx] = (uint32_t)k;
       c_next_work += (unsigned long long)delta_event_count<P>(w, count_events<P>(w, prm, set), d, prm, set);

@@ -466,6 +466,98 @@ DSL_HD int delta_event_count(const uint32_t* w, int parent_events, const Delta<P
   return n;
 }
 
+// ---- sleep sets ---------------------------------------------------------------------
+// Two deliveries to different nodes commute: parent G with message events A and B generates G+A
+// and G+B, and both later generate G+A+B. A frontier state P therefore carries a CREATOR record of
+// how it was first inserted -- the event Cr that made it from its recorded parent G, the node c
+// whose words Cr changed, and which of P's records are new against G -- and, when P is expanded,
+// a message event E (record r, destination e) SLEEPS when all of these hold:
+//   1. P has a creator record;
+//   2. r was already in G's network (its slot is not marked new);
+//   3. e != c, and e is an existing node;
+//   4. Cr is a timer event, or sleep_key(r) < sleep_key(rec(Cr)) (a tie: nobody sleeps).
+// A sleeping event is counted as a successor and never run: G+E exists at P's depth, still has Cr
+// enabled and reaches the same state, and the key rises strictly along such a chain, so some
+// state of the frontier runs the event. Timer events never sleep. The rule needs every frontier
+// state expanded with every record deliverable: the host switches it off (no creator is read)
+// for settings with a prune or a dropped link and for more than one shard.
+// A protocol opts out with `static constexpr bool kSleepSets = false`; one whose network holds
+// more than 64 records is out (the new-record mask is one 64-bit word).
+template <class P, class = void>
+struct SleepSets : std::integral_constant<bool, (P::kNetCap <= 64)> {};
+template <class P>
+struct SleepSets<P, std::void_t<decltype(P::kSleepSets)>>
+    : std::integral_constant<bool, (P::kSleepSets && P::kNetCap <= 64)> {};
+
+// What the settings must allow (the host decides once per search; the engine adds: one shard):
+// every record deliverable, and no prune -- a pruned state is not expanded, and the argument
+// needs every state of a level expanded. Goals and invariants end the search at their level.
+template <class P>
+inline bool sleep_sets_apply(const DevSettings& set) {
+  return SleepSets<P>::value && set.all_deliver != 0 && set.n_prune == 0;
+}
+
+// The creator word: has | timer | node c (6 bits) | the 24-bit key of Cr's record. 0 = none.
+constexpr uint32_t kCrHas = 1u << 31, kCrTimer = 1u << 30, kCrKeyMask = (1u << 24) - 1u;
+constexpr int kCrNodeShift = 24;
+// A fixed function of the record value alone.
+template <class Rec>
+DSL_HD uint32_t sleep_key(Rec r) {
+  const uint64_t x = (uint64_t)r;
+  return ((((uint32_t)x ^ ((uint32_t)(x >> 32) * 0x9E3779B1u)) * 0x85EBCA6Bu) >> 8) & kCrKeyMask;
+}
+
+// The creator word of a successor made by located event e of parent row w, which changed `node`.
+template <class P>
+DSL_HD uint32_t creator_word(const uint32_t* w, int e, int node) {
+  return kCrHas | ((uint32_t)node << kCrNodeShift) |
+         (e >= 0 ? sleep_key<typename P::Rec>(Net<P>::at(w, e)) : kCrTimer);
+}
+
+// The creator record of the successor (parent row w, located event e, delta d): the word, and the
+// mask of the merged record array's slots that the kept sends take (a kept send's slot is its
+// rank: the parent's records below it plus the kept sends below it, as emit_row places it).
+template <class P>
+DSL_HD void creator_record(const uint32_t* w, int e, const Delta<P>& d, uint32_t* cw, uint64_t* cm) {
+  using Rec = typename P::Rec;
+  const int n = Net<P>::size(w);
+  uint64_t m = 0;
+#pragma unroll
+  for (int i = 0; i < P::kMaxSends; i++) {
+    if (wave_none((d.keep >> i) != 0u)) break;
+    if ((d.keep >> i) & 1u) {
+      const Rec r = d.out.r[i];
+      int pos = 0;  // the parent's records below r: a fixed-trip lower bound (net_contains_fixed)
+#pragma unroll
+      for (int step = 1 << (31 - __builtin_clz((unsigned)P::kNetCap)); step > 0; step >>= 1) {
+        const int q = pos + step;
+        pos = (q <= n && Net<P>::at(w, q - 1) < r) ? q : pos;
+      }
+#pragma unroll
+      for (int j = 0; j < P::kMaxSends; j++)
+        if (j != i) pos += (((d.keep >> j) & 1u) && d.out.r[j] < r) ? 1 : 0;
+      m |= 1ull << (pos & 63);
+    }
+  }
+  *cm = m;
+  *cw = creator_word<P>(w, e, d.node);
+}
+
+// The branch-free test: record `idx` of the row (value r, destination `to`; `nodes` exist) sleeps
+// under the row's creator (cw, cm).
+template <class Rec>
+DSL_HD bool sleeping_rec(uint32_t cw, uint64_t cm, int idx, Rec r, int to, int nodes) {
+  const bool old = !((cm >> (idx & 63)) & 1ull);
+  const bool other = to != (int)((cw >> kCrNodeShift) & 63u) && to < nodes;
+  const bool lower = (cw & kCrTimer) != 0u || sleep_key<Rec>(r) < (cw & kCrKeyMask);
+  return (cw & kCrHas) != 0u && old && other && lower;
+}
+template <class P>
+DSL_HD bool sleeping(const uint32_t* w, uint32_t cw, uint64_t cm, int idx, const typename P::Params& prm) {
+  const auto r = Net<P>::at(w, idx);
+  return sleeping_rec<typename P::Rec>(cw, cm, idx, r, P::rec_to(r), P::num_nodes(prm));
+}
+
 // ---- merged-row emission ----------------------------------------------------------------------
 // The successor row = parent row with one node's words replaced and the canonical sends merged
 // into the sorted record array. The kernels write it lane-parallel (kernels.hpp: wave_emit):

@@ -28,6 +28,9 @@ struct Synthetic {
   // duplicates, profiles/r06_chunk_census.txt, but with the filter C3 d10 ran 7 % slower,
   // profiles/r06_c3_dedup_waves_ab.txt, and the routed levels 13 % slower,
   // profiles/r06_shard_scale_routedup16.txt.)
+  // No sleep sets (nodestate.hpp): 2 % of C3's events would sleep (its events are mostly timers),
+  // so its k_level stays the code it was.
+  static constexpr bool kSleepSets = false;
   static constexpr int kMsgClasses = 1;  // handler classes of messages (Poke); timers: class 1
   static constexpr int kTimerMin = 1, kTimerMax = 100;
   using Rec = uint32_t;

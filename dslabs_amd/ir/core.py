@@ -251,6 +251,9 @@ class Protocol:
         # no handler sends one record twice in one step: the device Sender skips its duplicate
         # check (P::kSendsDistinct; tests/hostcheck/protocheck.cpp counts violations)
         self.sends_distinct = False
+        # k_level's sleep sets (csrc/nodestate.hpp); False compiles the kernel without them
+        # (P::kSleepSets = false), for a protocol whose searches all prune
+        self.sleep_sets = True
         self.workload_size = ""       # Param name: commands per client, or fn(h, c) -> Expr (c from 0)
         self.predicates: List[PredDecl] = []
         # (client index c from 0, command k from 1) -> expected result Expr; < 0: not checked

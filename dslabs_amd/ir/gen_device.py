@@ -110,6 +110,8 @@ def generate(p: Protocol, source: str) -> str:
       f"kMaxSends = {p.max_sends};")
     if p.sends_distinct:
         a("  static constexpr bool kSendsDistinct = true;  // checked by tests/hostcheck (dup_sends)")
+    if not p.sleep_sets:
+        a("  static constexpr bool kSleepSets = false;  // no sleep sets in k_level (nodestate.hpp)")
     if p.net_preds():
         a("  static constexpr bool kNetPreds = true;  // a predicate reads the network (view_any_record)")
     a(f"  using Self = {N};")

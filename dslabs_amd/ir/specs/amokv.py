@@ -17,6 +17,7 @@ P.param_table("key", 3, 3, 0, 2)
 P.param_table("sym", 3, 3, 0, 3)
 P.param_table("expected", 3, 3, -1, (1 << 24) - 1, default=-1)
 P.workload_size = "ncmds"
+P.sleep_sets = False  # as the hand-written AmoKV: the lab's searches all prune, the rule would never run
 P.net_cap = 24
 P.max_sends = 1
 

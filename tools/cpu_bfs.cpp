@@ -74,6 +74,10 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
     uint32_t w[NW];
     Fp fp;
   };
+  struct Creator {  // DSL_CPU_SLEEP: a row's creator record (nodestate.hpp: sleep sets), cw 0: none
+    uint32_t cw = 0;
+    uint64_t cm = 0;
+  };
   Row init;
   if (!init_state<P>(init.w, prm)) return fprintf(stderr, "init overflow\n"), 2;
   if (!start.empty()) {  // a start state of an earlier search (the engine's dsl_set_initial)
@@ -86,6 +90,8 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
   // frontier buffers, one per thread and level parity: kept (with their capacity) across levels
   // and runs, as the engine keeps its device buffers across searches
   std::vector<std::vector<Row>> buf_a(threads), buf_b(threads);
+  // the rows' creator records, beside the frontier buffers; filled in DSL_CPU_SLEEP runs only
+  std::vector<std::vector<Creator>> cr_a(threads), cr_b(threads);
   std::vector<unsigned long long> per;
   int best = 99;
   const char* err = nullptr;
@@ -111,8 +117,12 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
   best = judge_view<P>(v0, prm, set, depth0, &pi);
   auto* cur = &buf_a;
   auto* nxt = &buf_b;
+  auto* ccur = &cr_a;
+  auto* cnxt = &cr_b;
   for (auto& v : *cur) v.clear();
+  for (auto& v : *ccur) v.clear();
   if (best < V_TERM_EXCEPTION) (*cur)[0].push_back(init);
+  if (best < V_TERM_EXCEPTION && getenv("DSL_CPU_SLEEP")) (*ccur)[0].push_back(Creator{});
   best = best >= V_TERM_EXCEPTION ? best : 99;
   // the frontier as (part, index) ranges: parts are the previous level's per-thread vectors
   for (int depth = depth0; best == 99 && !err; depth++) {
@@ -137,9 +147,18 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
     static const bool census = getenv("DSL_CPU_CENSUS") != nullptr;
     std::vector<std::array<unsigned long long, 5 * NC>> cen(threads);
     for (auto& c : cen) c.fill(0);
+    // DSL_CPU_SLEEP=1: the sleep-set census (k_level's rule, nodestate.hpp) -- per level the events,
+    // the sleeping events, those the no-op filter had not already taken, the handlers run and the
+    // probes, to stderr; every event still runs. DSL_CPU_SLEEP=2: sleeping events are skipped as
+    // k_level skips them (the recorded creator is the insert's winner among the racing threads).
+    static const int sleep_mode = getenv("DSL_CPU_SLEEP") ? atoi(getenv("DSL_CPU_SLEEP")) : 0;
+    const bool sleep_rule = sleep_mode && sleep_sets_apply<P>(set);
+    std::atomic<unsigned long long> sl_events{0}, sl_sleeping{0}, sl_unfiltered{0}, sl_run{0}, sl_probes{0};
     auto work = [&](int t) {
       std::vector<Row>& out = (*nxt)[t];
       out.clear();
+      std::vector<Creator>& cout = (*cnxt)[t];
+      cout.clear();
       unsigned long long c_new = 0;
       int my_best = 99, my_err = 0;
       Row s;
@@ -166,6 +185,17 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
               }
               cen[t][5 * real + (cls == Classes<P>::kSkip ? 1 : 0)]++;
             }
+            int located = INT32_MIN;
+            if (sleep_mode) {
+              const bool filtered = event_class_skip<P>(r.w, prm, set, k, &located) == Classes<P>::kSkip;
+              const Creator& rc0 = (*ccur)[part][g - start[part]];
+              const bool sl = sleep_rule && located >= 0 && sleeping<P>(r.w, rc0.cw, rc0.cm, located, prm);
+              sl_events++;
+              sl_sleeping += sl;
+              sl_unfiltered += sl && !filtered;
+              if (sl && sleep_mode == 2) continue;
+              sl_run += !filtered;
+            }
             const int rc = delta_step<P>(r.w, k, dl, prm, set);
             if (census && cls != Classes<P>::kSkip) {
               const bool nop = rc == STEP_OK && dl.keep == 0 && same_words<P::kNodeWords>(dl.nw, r.w + dl.node * P::kNodeWords);
@@ -187,6 +217,7 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
               cc_probed++;
               if (!local.insert(f.lo ^ (f.hi * 0x9E3779B97F4A7C15ull)).second) cc_dup++;
             }
+            if (sleep_mode) sl_probes++;
             const int ins = seen.insert(f);
             if (ins < 0) {
               my_err = 2;
@@ -212,6 +243,11 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
             }
             s.fp = f;
             out.push_back(s);
+            if (sleep_mode) {
+              Creator c;
+              if (sleep_rule) creator_record<P>(r.w, located, dl, &c.cw, &c.cm);
+              cout.push_back(c);
+            }
           }
         }
       }
@@ -244,10 +280,15 @@ int run(const dsl_protocol_desc& d, const dsl_settings& hs, int threads, int tab
       }
       fprintf(stderr, "\n");
     }
+    if (sleep_mode)
+      fprintf(stderr, "sleep census level %d (%s): events %llu, sleeping %llu, sleeping not filtered %llu, handlers run %llu, "
+              "probes %llu, new %llu\n", depth + 1, !sleep_rule ? "rule off" : sleep_mode == 2 ? "skipping" : "counting",
+              sl_events.load(), sl_sleeping.load(), sl_unfiltered.load(), sl_run.load(), sl_probes.load(), level_new.load());
     per.push_back(level_new.load());
     if (level_err) err = level_err == 2 ? "visited table full" : "network overflow";
     best = level_best.load();
     std::swap(cur, nxt);
+    std::swap(ccur, cnxt);
   }
   el = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   if (run > 0 || repeat == 1) {

@@ -261,36 +261,42 @@ __device__ __forceinline__ void block_flush(unsigned long long* red, unsigned lo
 }
 
 // Wave-cooperative row emission: every lane with `active` has a successor (its parent row
-// `base + pidx * STRIDE`, its canonical delta `d`) to be written to `dst`. The rows are written one
-// after another by the whole wavefront; the destination is never read back. Per row:
-//   - header words (node words, the record count, padding): lane o copies parent word o, or the
-//     replaced node's word, and writes it -- one coalesced 4-byte store per 64 words;
-//   - records: the merged record array is the parent's sorted records (lane q holds record q)
-//     plus the kept sends, placed in the lanes after them; an element's slot in the merged array
-//     is its rank: a parent record's is q + the new records below it (one compare per new record),
-//     a new record's is ONE ballot + popcount over all the elements (the parent's records below
-//     it plus the new records below it). Every lane then stores its element at its rank, and the
-//     free slots their zero -- one store instruction per 64 records, all within the row's record
-//     region (the memory pipeline coalesces by address, not lane order).
-// The source lane's delta is read with v_readlane into scalar registers (no LDS round trip per
-// field); everything is branch-free per lane (the per-word select chains of the r02 emitter
-// compiled to ~1,300 exec-mask instructions per Multi-Paxos row). Stores go through
-// address-space-1 pointers: a pointer that came through v_readlane would otherwise be a FLAT
-// store, which also counts in lgkmcnt. Must be called by all lanes of the wave.
-// Returns true (wave-uniform) when two kept sends of one row were equal: they would share a rank
-// and leave a record slot unwritten. Only a protocol whose Sender skips its duplicate check
-// (P::kSendsDistinct, asserted on the explored steps of tests/hostcheck) can get there; the caller
-// raises an error instead of writing a wrong row silently.
+// `base + pidx * STRIDE`, its canonical delta `d`) to be written to `dst`; the destination is never
+// read back. For a protocol of at most 64 records (the mask rule, nodestate.hpp: emit_row_masked):
+//   - a lane-parallel prepass, once per call: every active lane computes M, the mask of the merged
+//     record array's slots that its own kept sends take (delta_new_slots: a lower bound among the
+//     parent's records per kept send, in the owning lane), and stores each kept send at its slot
+//     itself, one 8-byte store per kept send;
+//   - then the rows are written one after another by the whole wavefront, and a row reads only
+//     pidx, dst, node and M from its source lane (v_readlane into scalar registers):
+//       header words (node words, the record count, padding): lane o copies parent word o, or the
+//       replaced node's word, and writes it -- one coalesced 4-byte store per 64 words;
+//       records: lane s, for a slot s < n + m that M does not mark, stores the parent's record
+//       s - (bits of M below s, one mbcnt) at slot s -- one read and one store in slot order, no
+//       instruction per send.
+// A protocol of more than 64 records (PingPongIR), or one that opts out (nodestate.hpp: MaskEmit;
+// PB), keeps the rank rule: the parent's records in
+// lanes [0, n), the kept sends read with one v_readlane each and placed in the lanes after them,
+// an element's slot is its rank (a parent record's is q + the new records below it, a new
+// record's ONE ballot + popcount over all the elements), and every lane stores its element at its
+// rank. Everything is branch-free per lane. Stores go through address-space-1 pointers: a pointer
+// that came through v_readlane would otherwise be a FLAT store, which also counts in lgkmcnt.
+// Only the row's n + m records are stored: the free slots after them (and the padding) keep
+// whatever the buffer held, since every reader of a row reads its records below the count
+// (Net::at for j < size; rows never leave the device: host states are rebuilt by replay).
+// Must be called by all lanes of the wave.
+// Returns true (wave-uniform) when two kept sends of one row were equal: they share a slot (M has
+// fewer bits than keep) and would leave a record slot unwritten. Only a protocol whose Sender
+// skips its duplicate check (P::kSendsDistinct, asserted on the explored steps of tests/hostcheck)
+// can get there; the caller raises an error instead of writing a wrong row silently.
 // nw_lds (k_level): the changed nodes' words already in LDS, kNodeWords per lane of the workgroup
 // (s_nodew; `lane0` = the wave's first lane there): a header word then comes from one LDS read
 // instead of kNodeWords readlanes and selects per row.
-// MASK (k_level with sleep sets; at most 64 records): when `want_mask` (wave-uniform), the lane that
-// owns a row also gets, in *new_mask, the mask of the merged array's slots that its kept sends
-// took -- the ranks this emission gave them, which are creator_record's slots (nodestate.hpp): one
-// readlane per kept send instead of a lower bound per send in the owning lane.
-template <class P, int STRIDE = Layout<P>::kWords, bool MASK = false>
+// new_mask (k_level with sleep sets; at most 64 records): an active lane gets M there, which is
+// creator_record's mask (nodestate.hpp).
+template <class P, int STRIDE = Layout<P>::kWords>
 __device__ __forceinline__ bool wave_emit(bool active, const uint32_t* base, uint64_t pidx, const Delta<P>& d,
-                                          uint32_t* dst, const uint32_t* nw_lds = nullptr, bool want_mask = false,
+                                          uint32_t* dst, const uint32_t* nw_lds = nullptr,
                                           uint64_t* new_mask = nullptr) {
   bool collision = false;
   using L = Layout<P>;
@@ -301,17 +307,35 @@ __device__ __forceinline__ bool wave_emit(bool active, const uint32_t* base, uin
   constexpr int TH = (L::kRecBase + 63) / 64;                         // header words per lane
   constexpr int TR = (P::kNetCap + 63) / 64;                          // records per lane
   constexpr int TAIL0 = L::kRecBase + P::kNetCap * L::kRecWords;      // padding after the records
+  constexpr bool MASKED = MaskEmit<P>::value;
   static_assert(NW - TAIL0 <= 64, "at most 64 padding words after the records");
-  unsigned long long mask = __ballot(active);
   const int lane = __lane_id();
+  [[maybe_unused]] uint64_t M = 0;
+  if constexpr (MASKED) {
+    grec* own = (grec*)((uint64_t)(uintptr_t)dst + (uint64_t)L::kRecBase * 4u);
+    M = delta_new_slots<P>(base + pidx * STRIDE, d, active ? d.keep : 0u, [&](int, int slot, Rec r) {
+      if (slot < P::kNetCap) own[slot] = r;  // n + m <= kNetCap is the caller's: never past the row
+    });
+    collision = __ballot(active && __popcll(M) != __builtin_popcount(d.keep)) != 0ull;
+    if (new_mask && active) *new_mask = M;
+  }
+  unsigned long long mask = __ballot(active);
   while (mask) {
     const int src = __ffsll((long long)mask) - 1;
     mask &= mask - 1;
     const uint32_t* pw = base + rl64(pidx, src) * STRIDE;
     g32* ow = (g32*)(rl64((uint64_t)(uintptr_t)dst, src));
     const int node = (int)rl32((uint32_t)d.node, src);
-    const uint32_t keep = rl32(d.keep, src);
-    const int m = __builtin_popcount(keep);
+    [[maybe_unused]] uint32_t keep = 0;
+    [[maybe_unused]] uint64_t ms = 0;
+    int m;
+    if constexpr (MASKED) {
+      ms = rl64(M, src);
+      m = __popcll(ms);
+    } else {
+      keep = rl32(d.keep, src);
+      m = __builtin_popcount(keep);
+    }
     const int n = Net<P>::size(pw);
     // header
     if (nw_lds) {
@@ -342,21 +366,27 @@ __device__ __forceinline__ bool wave_emit(bool active, const uint32_t* base, uin
         }
       }
     }
-    // records: the parent's in lanes [0, n), the kept sends in lanes [n, n + m)
-    Rec e[TR];
-    int rk[TR];
+    grec* orec = (grec*)(ow + L::kRecBase);
+    if constexpr (MASKED) {
+      // the parent's records, in slot order around the kept sends' slots (stored by the prepass)
+      const int below = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(ms >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)ms, 0u));
+      const bool isnew = (ms >> lane) & 1ull;
+      if (lane < n + m && !isnew) orec[lane] = Net<P>::at(pw, lane - below);
+    } else {
+      // records: the parent's in lanes [0, n), the kept sends in lanes [n, n + m)
+      Rec e[TR];
+      int rk[TR];
 #pragma unroll
-    for (int t = 0; t < TR; t++) {
-      const int q = lane + 64 * t;
-      e[t] = q < n ? Net<P>::at(pw, q) : ~(Rec)0;
-      rk[t] = q;
-    }
-    // the kept sends, one pass: send i goes to lane q (the next free one) with rank pos = the
-    // elements already placed below it (parents and earlier sends; free lanes hold ~0, never
-    // below), and every placed element above it moves up one -- a later, smaller send then raises
-    // the earlier sends' ranks the same way, so the ranks end as the merged order's slots (one
-    // readlane per kept send and one scalar test per possible send; it was two of each)
-    {
+      for (int t = 0; t < TR; t++) {
+        const int q = lane + 64 * t;
+        e[t] = q < n ? Net<P>::at(pw, q) : ~(Rec)0;
+        rk[t] = q;
+      }
+      // the kept sends, one pass: send i goes to lane q (the next free one) with rank pos = the
+      // elements already placed below it (parents and earlier sends; free lanes hold ~0, never
+      // below), and every placed element above it moves up one -- a later, smaller send then raises
+      // the earlier sends' ranks the same way, so the ranks end as the merged order's slots (one
+      // readlane per kept send and one scalar test per possible send)
       int q = n;
 #pragma unroll
       for (int i = 0; i < P::kMaxSends; i++) {  // constant indices: the send list stays in VGPRs
@@ -384,24 +414,11 @@ __device__ __forceinline__ bool wave_emit(bool active, const uint32_t* base, uin
           q++;
         }
       }
-    }
-    if constexpr (MASK) {
-      static_assert(TR == 1, "the new-record mask is one 64-bit word");
-      if (want_mask) {  // lanes [n, n + m) hold the kept sends, rk[0] their slots
-        const int n0 = __builtin_amdgcn_readfirstlane(n);
-        unsigned long long nm = 0;
-        for (int s = n0; s < n0 + m; s++) nm |= 1ull << (rl32((uint32_t)rk[0], s & 63) & 63u);
-        if (lane == src) *new_mask = nm;
-      }
-    }
-    // only the row's n + m records are stored: the free slots after them (and the padding) keep
-    // whatever the buffer held, since every reader of a row reads its records below the count
-    // (Net::at for j < size; rows never leave the device: host states are rebuilt by replay)
-    grec* orec = (grec*)(ow + L::kRecBase);
 #pragma unroll
-    for (int t = 0; t < TR; t++) {
-      const int q = lane + 64 * t;
-      if (q < n + m) orec[rk[t]] = e[t];
+      for (int t = 0; t < TR; t++) {
+        const int x = lane + 64 * t;
+        if (x < n + m) orec[rk[t]] = e[t];
+      }
     }
   }
   return collision;
@@ -1187,11 +1204,10 @@ k_level(LevelArgs<P> a, typename P::Params prm, DevSettings set) {
           }
           bool coll;
           [[maybe_unused]] uint64_t ncm = 0;  // sleep sets: the slots of this lane's row that its kept sends take
-          [[maybe_unused]] bool want_mask = false;
-          if constexpr (SLEEP) want_mask = a.sleep != 0;
+          static_assert(!SLEEP || LaneEmit<P>::value || MaskEmit<P>::value, "the creator's mask comes from the mask rule");
           if constexpr (LaneEmit<P>::value) coll = lane_emit<P>(fits, rows + j * SP, d, a.next + idx * NW);
-          else coll = wave_emit<P, SP, SLEEP>(fits, rows, (uint64_t)j, d, a.next + idx * NW,
-                                              s_nodew + (tid - lane) * P::kNodeWords, want_mask, &ncm);
+          else coll = wave_emit<P, SP>(fits, rows, (uint64_t)j, d, a.next + idx * NW,
+                                       s_nodew + (tid - lane) * P::kNodeWords, SLEEP ? &ncm : nullptr);
           if constexpr (SLEEP) {
             // the successor's creator record (every record is deliverable: event k < size is record k)
             if (a.sleep && fits) {

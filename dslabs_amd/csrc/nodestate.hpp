@@ -514,18 +514,22 @@ DSL_HD uint32_t creator_word(const uint32_t* w, int e, int node) {
          (e >= 0 ? sleep_key<typename P::Rec>(Net<P>::at(w, e)) : kCrTimer);
 }
 
-// The creator record of the successor (parent row w, located event e, delta d): the word, and the
-// mask of the merged record array's slots that the kept sends take (a kept send's slot is its
-// rank: the parent's records below it plus the kept sends below it, as emit_row places it).
-template <class P>
-DSL_HD void creator_record(const uint32_t* w, int e, const Delta<P>& d, uint32_t* cw, uint64_t* cm) {
+// The slots of the merged record array that the sends of d marked in `keep` take (parent row w;
+// at most 64 records): a kept send's slot is its rank, the parent's records below it plus the kept
+// sends below it, as emit_row places it. Calls visit(i, slot, record) for every kept send i (i is
+// a compile-time constant after unrolling: the send list stays in VGPRs) and returns the mask of
+// the slots. Two equal kept sends share a slot: the mask then has fewer bits than `keep`.
+// One copy of the rule for creator_record, emit_row_masked and the kernels' wave_emit. On the
+// device every lane of the wave calls it, a lane without a row with keep = 0 (it reads nothing).
+template <class P, class V>
+DSL_HD uint64_t delta_new_slots(const uint32_t* w, const Delta<P>& d, uint32_t keep, V visit) {
   using Rec = typename P::Rec;
-  const int n = Net<P>::size(w);
+  const int n = keep ? Net<P>::size(w) : 0;
   uint64_t m = 0;
 #pragma unroll
   for (int i = 0; i < P::kMaxSends; i++) {
-    if (wave_none((d.keep >> i) != 0u)) break;
-    if ((d.keep >> i) & 1u) {
+    if (wave_none((keep >> i) != 0u)) break;  // no lane keeps a later send
+    if ((keep >> i) & 1u) {
       const Rec r = d.out.r[i];
       int pos = 0;  // the parent's records below r: a fixed-trip lower bound (net_contains_fixed)
 #pragma unroll
@@ -535,11 +539,19 @@ DSL_HD void creator_record(const uint32_t* w, int e, const Delta<P>& d, uint32_t
       }
 #pragma unroll
       for (int j = 0; j < P::kMaxSends; j++)
-        if (j != i) pos += (((d.keep >> j) & 1u) && d.out.r[j] < r) ? 1 : 0;
+        if (j != i) pos += (((keep >> j) & 1u) && d.out.r[j] < r) ? 1 : 0;
       m |= 1ull << (pos & 63);
+      visit(i, pos, r);
     }
   }
-  *cm = m;
+  return m;
+}
+
+// The creator record of the successor (parent row w, located event e, delta d): the word, and the
+// mask of the merged record array's slots that the kept sends take (delta_new_slots).
+template <class P>
+DSL_HD void creator_record(const uint32_t* w, int e, const Delta<P>& d, uint32_t* cw, uint64_t* cm) {
+  *cm = delta_new_slots<P>(w, d, d.keep, [](int, int, typename P::Rec) {});
   *cw = creator_word<P>(w, e, d.node);
 }
 
@@ -566,7 +578,9 @@ DSL_HD bool sleeping(const uint32_t* w, uint32_t cw, uint64_t cm, int idx, const
 // below it), a new record r to slot (parent records below r) + (new records below r) -- its rank
 // among all the elements, as the records are distinct -- and the slots past n + m are zero.
 // emit_row restates exactly that element-wise rule on the host (tests/hostcheck checks it
-// against materialize(), which inserts the records one by one).
+// against materialize(), which inserts the records one by one). For a protocol of at most 64
+// records wave_emit writes the same row from the mask of the new records' slots
+// (emit_row_masked below, held against emit_row by tests/hostcheck/emitcheck.cpp).
 template <class P>
 DSL_HD bool emit_row(const uint32_t* pw, const Delta<P>& d, uint32_t* out) {
   using L = Layout<P>;
@@ -601,6 +615,46 @@ DSL_HD bool emit_row(const uint32_t* pw, const Delta<P>& d, uint32_t* out) {
     for (int j = 0; j < m; j++) pos += s[j] < s[i];
     put(pos, s[i]);
   }
+  return true;
+}
+
+// Which rule wave_emit writes a protocol's rows by: the mask rule (below) where the record array
+// fits one 64-bit mask, unless the protocol opts out with `static constexpr bool kMaskEmit = false`
+// (PB: its steps add at most one new record, so the rank rule's per-send loop is short, and the
+// mask rule's prepass ran the C4 search 1 % slower, profiles/emit_mask_ab.txt).
+template <class P, class = void>
+struct MaskEmit : std::integral_constant<bool, (P::kNetCap <= 64)> {};
+template <class P>
+struct MaskEmit<P, std::void_t<decltype(P::kMaskEmit)>>
+    : std::integral_constant<bool, (P::kMaskEmit && P::kNetCap <= 64)> {};
+
+// The mask rule: what wave_emit executes for a protocol of at most 64 records, restated
+// element-wise (tests/hostcheck/emitcheck.cpp holds it against emit_row on every successor).
+// M = delta_new_slots' mask, m its bit count: a kept send is stored at its slot; every other slot
+// s < n + m takes the parent's record s - (bits of M below s). *mask = M; *collision = two kept
+// sends were equal (M has fewer bits than keep: the caller raises an error, the row is not used).
+template <class P>
+DSL_HD bool emit_row_masked(const uint32_t* pw, const Delta<P>& d, uint32_t* out, uint64_t* mask, bool* collision) {
+  using L = Layout<P>;
+  using Rec = typename P::Rec;
+  static_assert(P::kNetCap <= 64, "the new-record mask is one 64-bit word");
+  const int n = Net<P>::size(pw);
+  if (n + delta_new_count<P>(d) > P::kNetCap) return false;
+  for (int o = L::kRecBase; o < L::kWords; o++) out[o] = 0u;
+  const uint64_t M = delta_new_slots<P>(pw, d, d.keep, [&](int, int slot, Rec r) { Net<P>::put(out, slot, r); });
+  const int m = __builtin_popcountll(M);
+  for (int o = 0; o < L::kRecBase; o++) {
+    uint32_t v = o < L::kNetCount ? pw[o] : o == L::kNetCount ? (uint32_t)(n + m) : 0u;
+    const int rel = o - d.node * P::kNodeWords;
+    if (rel >= 0 && rel < P::kNodeWords) v = d.nw[rel];
+    out[o] = v;
+  }
+  for (int s = 0; s < n + m; s++) {
+    if ((M >> s) & 1ull) continue;
+    Net<P>::put(out, s, Net<P>::at(pw, s - __builtin_popcountll(M & ((1ull << s) - 1ull))));
+  }
+  *mask = M;
+  *collision = m != delta_new_count<P>(d);
   return true;
 }
 

@@ -29,6 +29,7 @@ namespace dsl {
 struct PBIR {
   static constexpr int kNodes = 6, kNodeWords = 3, kNetCap = 64, kMaxSends = 3;
   static constexpr bool kSleepSets = false;  // no sleep sets in k_level (nodestate.hpp)
+  static constexpr bool kMaskEmit = false;  // rows by the rank rule (nodestate.hpp: MaskEmit)
   static constexpr bool kNetPreds = true;  // a predicate reads the network (view_any_record)
   using Self = PBIR;
   static constexpr int kMsgClasses = 9;

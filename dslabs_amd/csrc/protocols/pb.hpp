@@ -35,6 +35,9 @@ struct PB {
   // No sleep sets (nodestate.hpp): the lab's searches all prune (CLIENTS_DONE, hasViewReply), which
   // switches the rule off, and the kernel compiled with it ran the C4 search 3 % slower.
   static constexpr bool kSleepSets = false;
+  // Rows by the rank rule (nodestate.hpp: MaskEmit): a step adds at most one new record, and the
+  // mask rule's prepass ran the C4 search 1 % slower (profiles/emit_mask_ab.txt).
+  static constexpr bool kMaskEmit = false;
   static constexpr int kMsgClasses = 9;  // handler classes of messages (message types 0..8); timers: class 9
   static constexpr int kMaxView = 15;
   static constexpr bool kNetPreds = true;  // hasViewReply(n, p, b) and initView's goal read the network

@@ -254,6 +254,9 @@ class Protocol:
         # k_level's sleep sets (csrc/nodestate.hpp); False compiles the kernel without them
         # (P::kSleepSets = false), for a protocol whose searches all prune
         self.sleep_sets = True
+        # wave_emit's mask rule (csrc/nodestate.hpp: MaskEmit); False keeps the rank rule
+        # (P::kMaskEmit = false), for a protocol whose steps add at most one new record
+        self.mask_emit = True
         self.workload_size = ""       # Param name: commands per client, or fn(h, c) -> Expr (c from 0)
         self.predicates: List[PredDecl] = []
         # (client index c from 0, command k from 1) -> expected result Expr; < 0: not checked

@@ -112,6 +112,8 @@ def generate(p: Protocol, source: str) -> str:
         a("  static constexpr bool kSendsDistinct = true;  // checked by tests/hostcheck (dup_sends)")
     if not p.sleep_sets:
         a("  static constexpr bool kSleepSets = false;  // no sleep sets in k_level (nodestate.hpp)")
+    if not p.mask_emit:
+        a("  static constexpr bool kMaskEmit = false;  // rows by the rank rule (nodestate.hpp: MaskEmit)")
     if p.net_preds():
         a("  static constexpr bool kNetPreds = true;  // a predicate reads the network (view_any_record)")
     a(f"  using Self = {N};")

@@ -33,6 +33,7 @@ P.param_table("sym", 2, 3, 0, 3)
 P.param_table("expected", 2, 3, -1, 1023, default=-1)
 P.workload_size = "ncmds"
 P.sleep_sets = False  # as the hand-written PB: the lab's searches all prune, the rule would never run
+P.mask_emit = False  # as the hand-written PB: a step adds at most one new record, the rank rule is the faster one
 P.expected_result = lambda c, k: Expr(f"sel_param(p.expected, {c.dev}, {k.dev} - 1)",
                                       f"prm.expected[{c.orc}][{k.orc} - 1]")
 P.net_cap = 64

@@ -6,9 +6,10 @@ include/dslabs_hip.h); this package is the thin host-side mirror of the referenc
 """
 from .search import (CLIENTS_DONE, NONE_DECIDED, RESULTS_OK, EndCondition, Engine, EventCount, FieldRef,  # noqa: F401
                      MessagePattern, PredicateResult, Search, SearchResults, SearchSettings, SearchState, StatePredicate, allOf,
-                     anyOf, clientDone, clientHasResults, field_value, message_matches, statePredicate)
+                     anyOf, clientDone, clientHasResults, field_value, message_matches, new, old, statePredicate,
+                     StepFieldRef, StepViolation)
 
 __all__ = ["Search", "SearchSettings", "SearchState", "SearchResults", "EndCondition", "StatePredicate",
            "PredicateResult", "Engine", "RESULTS_OK", "CLIENTS_DONE", "NONE_DECIDED", "clientDone",
            "clientHasResults", "FieldRef", "statePredicate", "allOf", "anyOf", "field_value", "MessagePattern",
-           "message_matches", "EventCount"]
+           "message_matches", "EventCount", "old", "new", "StepFieldRef", "StepViolation"]

@@ -18,6 +18,7 @@ DSL_MAX_NODES = 32
 DSL_MAX_PREDICATES = 16
 DSL_MAX_POOL = 48
 DSL_MAX_WATCHES = 8
+DSL_MAX_STEP_INVARIANTS = 8
 DSL_MAX_PARAMS = 64
 DSL_MAX_EVENT_FIELDS = 8
 DSL_PROTO_PINGPONG_IR = 8  # protocols generated from the IR (dslabs_amd/ir/specs)
@@ -42,7 +43,7 @@ EXPORTED = [
     "dsl_run_dfs", "dsl_replay", "dsl_human_readable_trace", "dsl_set_dropped",
     "dsl_set_watches", "dsl_watch_counts", "dsl_set_watch_witnesses", "dsl_watch_witness",
     "dsl_event_class_count", "dsl_event_class_name", "dsl_event_class_is_timer", "dsl_set_event_census",
-    "dsl_event_census",
+    "dsl_event_census", "dsl_set_step_invariants", "dsl_step_edges", "dsl_step_violation",
 ]
 DSL_ABI_VERSION = 6  # include/dslabs_hip.h; load() refuses a library of another layout
 
@@ -188,6 +189,13 @@ def load() -> ctypes.CDLL:
     lib.dsl_event_class_is_timer.argtypes = [P(dsl_protocol_desc), ctypes.c_int32]
     lib.dsl_set_event_census.argtypes = [ctypes.c_void_p, ctypes.c_int32]
     lib.dsl_event_census.argtypes = [ctypes.c_void_p, ctypes.c_int32, P(dsl_event_count), P(ctypes.c_int32)]
+    lib.dsl_set_step_invariants.argtypes = [ctypes.c_void_p, P(dsl_predicate), ctypes.c_int32, P(dsl_predicate),
+                                            ctypes.c_int32]
+    lib.dsl_step_edges.argtypes = [ctypes.c_void_p, P(ctypes.c_uint64), ctypes.c_int32, P(ctypes.c_int32),
+                                   P(ctypes.c_uint64)]
+    lib.dsl_step_violation.argtypes = [ctypes.c_void_p, P(ctypes.c_int32), P(ctypes.c_int32), P(ctypes.c_uint64),
+                                       P(ctypes.c_uint64), P(dsl_event), ctypes.c_int32, P(ctypes.c_int32),
+                                       P(ctypes.c_uint8), P(ctypes.c_uint8), ctypes.c_size_t]
     lib.dsl_run.argtypes = [ctypes.c_void_p, P(P(dsl_result))]
     lib.dsl_run_dfs.argtypes = [ctypes.c_void_p, P(dsl_dfs_config), P(P(dsl_result))]
     lib.dsl_replay.argtypes = [ctypes.c_void_p, P(dsl_event), ctypes.c_int32, ctypes.c_int32, P(P(dsl_result))]

@@ -34,7 +34,7 @@ namespace dsl {
 
 void set_error(const std::string& msg);
 int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out,
-                     const WatchList* watches = nullptr);
+                     const WatchList* watches = nullptr, const StepList* steps = nullptr, DevStep* step_out = nullptr);
 
 #define DSL_HIP(call)                                                                           \
   do {                                                                                          \
@@ -114,7 +114,21 @@ struct EngineBase {
   static constexpr size_t kEventWords = (size_t)DSL_EVENT_CLASSES * DSL_EVENT_NODES * 4;
   std::vector<std::vector<uint64_t>> event_census;
   bool event_census_on = false;
+  // step invariants (dsl_set_step_invariants): the last run()'s judged edges per completed level
+  // and its violation (index -1 = none). They live and die with the census.
+  virtual int set_step_invariants(const dsl_predicate* p, int n, const dsl_predicate* pool, int n_pool) = 0;
+  std::vector<uint64_t> step_edges;
+  struct StepViolation {
+    int32_t index = -1, depth = -1;
+    uint64_t edges = 0;
+    uint64_t per_invariant[DSL_MAX_STEP_INVARIANTS] = {};
+    std::vector<dsl_event> trace;
+    std::vector<uint8_t> parent, state;
+  };
+  StepViolation step_violation;
   void clear_census() {
+    step_edges.clear();
+    step_violation = StepViolation{};
     watch_census.clear();
     watch_total.clear();
     watch_witness.clear();
@@ -377,6 +391,8 @@ struct BfsEngine : EngineBase {
     (void)hipFree(t0_rt);
     (void)hipFree(ev_dev);
     if (ev_host) (void)hipHostFree(ev_host);
+    (void)hipFree(step_dev);
+    if (step_host) (void)hipHostFree(step_host);
     if (xhost) (void)hipHostFree(xhost);
     if (hq) (void)hipHostFree(hq);
     for (auto e : qev) (void)hipEventDestroy(e);
@@ -388,7 +404,7 @@ struct BfsEngine : EngineBase {
   }
 
   int state_bytes() const override { return (int)sizeof(typename P::State); }
-  int set_settings(const dsl_settings& s) override { return resolve_all(s, hwatch, hwpool); }
+  int set_settings(const dsl_settings& s) override { return resolve_all(s, hwatch, hwpool, hstep, hspool); }
   // The watches (dsl_set_watches), kept across set_settings like the dropped set: the settings and
   // the watches are compiled together (one ops[], one rec_conds[]), so whichever call comes second
   // and makes a sum overflow is the one refused, and the engine keeps what it had.
@@ -403,11 +419,31 @@ struct BfsEngine : EngineBase {
       return DSL_ERR_ARG;
     }
     const std::vector<dsl_predicate> nw(w, w + n), np(pool, pool + (n ? n_pool : 0));
-    const int rc = resolve_all(hset, nw, np);
+    const int rc = resolve_all(hset, nw, np, hstep, hspool);
     if (rc == DSL_OK) {
       clear_census();
       witness_mask = 0;  // the requests belong to the watches they were made for
     }
+    return rc;
+  }
+  // The step invariants (dsl_set_step_invariants), kept and compiled as the watches are: behind
+  // everything else, described by dstep (k_step_check's own argument; DevSettings keeps its layout).
+  std::vector<dsl_predicate> hstep, hspool;
+  DevStep dstep{};
+  unsigned long long* step_dev = nullptr;   // k_step_check's counters (kStepWords)
+  unsigned long long* step_host = nullptr;  // ... and their pinned host copy
+  int set_step_invariants(const dsl_predicate* q, int n, const dsl_predicate* pool, int n_pool) override {
+    if (n < 0 || n > DSL_MAX_STEP_INVARIANTS) {
+      set_error("step invariants: " + std::to_string(n) + ", outside 0.." + std::to_string(DSL_MAX_STEP_INVARIANTS));
+      return DSL_ERR_ARG;
+    }
+    if ((n > 0 && !q) || n_pool < 0 || n_pool > DSL_MAX_POOL || (n_pool > 0 && !pool)) {
+      set_error("step invariants: predicate counts out of range");
+      return DSL_ERR_ARG;
+    }
+    const std::vector<dsl_predicate> ns(q, q + n), np(pool, pool + (n ? n_pool : 0));
+    const int rc = resolve_all(hset, hwatch, hwpool, ns, np);
+    if (rc == DSL_OK) clear_census();
     return rc;
   }
   // The event census's device buffer (k_event_census's `out`) and its pinned host copy.
@@ -426,13 +462,17 @@ struct BfsEngine : EngineBase {
     witness_mask = mask;
     return DSL_OK;
   }
-  int resolve_all(const dsl_settings& s, const std::vector<dsl_predicate>& w, const std::vector<dsl_predicate>& wp) {
+  int resolve_all(const dsl_settings& s, const std::vector<dsl_predicate>& w, const std::vector<dsl_predicate>& wp,
+                  const std::vector<dsl_predicate>& st, const std::vector<dsl_predicate>& stp) {
     DevSettings ds;
+    DevStep dst;
     const WatchList wl{w.data(), (int32_t)w.size(), wp.data(), (int32_t)wp.size()};
-    int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &ds, &wl);
+    const StepList sl{st.data(), (int32_t)st.size(), stp.data(), (int32_t)stp.size()};
+    int rc = resolve_settings(s, P::num_nodes(prm), &P::known_predicate, &ds, &wl, &sl, &dst);
     if (rc == DSL_OK) {
       std::string why;
-      if (!check_field_leaves<P>(ds, &why) || !check_net_leaves<P>(ds, &why)) {  // the checks that need P
+      if (!check_field_leaves<P>(ds, &why) || !check_net_leaves<P>(ds, &why) ||
+          !check_step_leaves<P>(ds, dst, prm, &why)) {  // the checks that need P
         set_error(why);
         return DSL_ERR_ARG;  // the engine keeps the settings and the watches it had
       }
@@ -440,6 +480,9 @@ struct BfsEngine : EngineBase {
       hset = s;
       hwatch = w;
       hwpool = wp;
+      hstep = st;
+      hspool = stp;
+      dstep = dst;
       set_pred_reads<P>(dset, prm);
       // a search with watches launches the FIELD instantiation even when every watch is a named
       // leaf: the watch code lives in k_level<P, false, true> alone (no further instantiation)
@@ -1866,6 +1909,13 @@ struct BfsEngine : EngineBase {
                 " shards): run it with virtual_shards = 1 and world_size = 1, or turn it off (dsl_set_event_census)");
       return DSL_ERR_ARG;
     }
+    // step invariants are single-shard too: the pass reads no table and each shard could run it over
+    // its own frontier, but the ranks do not yet agree on the end of the search it asks for
+    if (dstep.n_step > 0 && W > 1) {
+      set_error("step invariants are not supported in a search over more than one shard (" + std::to_string(W) +
+                " shards): run it with virtual_shards = 1 and world_size = 1, or clear them (dsl_set_step_invariants)");
+      return DSL_ERR_ARG;
+    }
     restart_buckets = 0;
     t_run0 = std::chrono::steady_clock::now();
     for (int attempt = 0;; attempt++) {
@@ -1902,6 +1952,12 @@ struct BfsEngine : EngineBase {
     uint64_t new_states = 0, rows = 0, successors = 0, err_overflow = 0, err_table = 0, err_frontier = 0;
     uint64_t work = 0, parents = 0;
   };
+  struct StepFound {  // the reported violating edge: its chain's raw event indices, E last
+    int32_t index = -1, depth = -1;
+    uint64_t edges = 0;
+    uint64_t per_invariant[DSL_MAX_STEP_INVARIANTS] = {};
+    std::vector<uint32_t> events;
+  };
   struct SearchRun {
     bool use_queue = false, trace_levels = false;
     bool over = false;  // a step ended the search: the level loop stops
@@ -1923,6 +1979,12 @@ struct BfsEngine : EngineBase {
     // level; ev_pending: this level's pass ran and its counts came back with the level's counters
     std::vector<std::vector<uint64_t>> events;
     bool ev_pending = false;
+    // step invariants of this attempt (a restarted search counts from zero): the judged edges per
+    // completed level; st_pending: this level's pass ran and its counters came back with the
+    // level's own; the violation, once found (sv.depth >= 0)
+    std::vector<uint64_t> step_edges;
+    bool st_pending = false;
+    StepFound sv;
     // a sharded level's gathered records already hold the next level's global frontier size, work
     // and time-up flag (LevelPlan::g): no collective at the top of that next level
     bool have_g = false;
@@ -2028,7 +2090,12 @@ struct BfsEngine : EngineBase {
     // do_checks reads every level's rows right after the level: no device-side queue of levels
     // ... and the event census runs its pass before every level's k_level, on the table as it
     // stands then
-    r.use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE && !event_census_on;
+    // ... and so does the step invariants' pass, over the frontier in `cur`
+    r.use_queue = !getenv("DSL_NO_QUEUE") && hset.do_checks == DSL_CHECKS_NONE && !event_census_on && dstep.n_step == 0;
+    if (dstep.n_step) {
+      if (!step_dev) DSL_HIP(hipMalloc(&step_dev, kStepWords * 8));
+      if (!step_host) DSL_HIP(hipHostMalloc(&step_host, kStepWords * 8));
+    }
     sleep_on = sleep_allowed();
     if (event_census_on) {
       if (!ev_dev) DSL_HIP(hipMalloc(&ev_dev, kEventWords * 8));
@@ -2294,11 +2361,100 @@ struct BfsEngine : EngineBase {
     return DSL_OK;
   }
 
+  // The step invariants' pass over the level about to run (single shard, never queued), in the
+  // census's slot: its counters zeroed on the stream, then k_step_check (find = 0) over the frontier.
+  StepArgs<P> step_args(const Shard& S, int parent_depth, const PassShape& shape) const {
+    StepArgs<P> a{};
+    a.cur = S.cur;
+    a.cur_fp = S.cur_fp;
+    a.segs = shape.segs;
+    a.incremental = parent_depth > init_depth ? 1 : 0;
+    a.step = dstep;
+    a.ctr = step_dev;
+    return a;
+  }
+  int enqueue_step_check(SearchRun& r) {
+    r.st_pending = false;
+    if (!dstep.n_step) return DSL_OK;
+    Shard& S = sh[0];
+    if (S.F == 0) return DSL_OK;
+    DSL_HIP(hipMemsetAsync(step_dev, 0, kStepWords * 8, stream));
+    const PassShape shape = reexpand_shape(S);
+    const StepArgs<P> a = step_args(S, r.depth, shape);
+    hipLaunchKernelGGL(k_step_check<P>, dim3(shape.blocks), dim3(kBlock), shape.lds, stream, a, prm, dset);
+    DSL_HIP(hipGetLastError());
+    r.st_pending = true;
+    return DSL_OK;
+  }
+  // The reported edge of the level whose pass counted a violation, while its parents are still in
+  // S.cur (parent_depth: their depth): k_step_check with find = 1 -- the records whose parent's hi is
+  // the minimum -- one round trip, again at the exact size if they ran past their room; the smallest
+  // (pf.lo, event) of them; the parent's chain through the history arena (walk_chains, which
+  // expects the level's entry in level_size).
+  int find_step_violation(SearchRun& r, int parent_depth) {
+    Shard& S = sh[0];
+    DevBufs bufs;
+    const PassShape shape = reexpand_shape(S);
+    StepArgs<P> a = step_args(S, parent_depth, shape);
+    a.find = 1;
+    a.cap = 1024;
+    DSL_TRY(bufs.get(&a.out, a.cap * sizeof(StepRec)));
+    const uint64_t key = ~(uint64_t)step_host[kStepBest];
+    std::vector<StepRec> recs;
+    unsigned long long n_out = 0;
+    for (int pass = 0; pass < 2; pass++) {  // the second only when the records ran past their room
+      hipLaunchKernelGGL(k_step_check<P>, dim3(shape.blocks), dim3(kBlock), shape.lds, stream, a, prm, dset);
+      DSL_HIP(hipGetLastError());
+      DSL_HIP(hipMemcpyAsync(&n_out, step_dev + kStepOut, 8, hipMemcpyDeviceToHost, stream));
+      recs.resize(a.cap);
+      DSL_HIP(hipMemcpyAsync(recs.data(), a.out, a.cap * sizeof(StepRec), hipMemcpyDeviceToHost, stream));
+      DSL_TRY(hsync());
+      if (n_out <= a.cap) break;
+      if (pass) {
+        set_error("step invariants: the record pass overflowed at its exact size");
+        return DSL_ERR_ARG;
+      }
+      a.cap = n_out;
+      DSL_TRY(bufs.get(&a.out, a.cap * sizeof(StepRec)));
+      DSL_HIP(hipMemsetAsync(step_dev + kStepOut, 0, 8, stream));
+    }
+    recs.resize(n_out);
+    const StepRec* pick = nullptr;
+    for (const auto& x : recs) {
+      if (x.pf.hi != key) continue;
+      if (!pick || std::make_tuple(x.pf.lo, x.event) < std::make_tuple(pick->pf.lo, pick->event)) pick = &x;
+    }
+    if (!pick) {
+      set_error("step invariants: no violating edge of depth " + std::to_string(parent_depth) + " carries the minimum key");
+      return DSL_ERR_ARG;
+    }
+    r.sv.index = (int32_t)pick->index;
+    r.sv.depth = parent_depth + 1;
+    r.sv.edges = step_host[kStepViolating];
+    for (int q = 0; q < DSL_MAX_STEP_INVARIANTS; q++) r.sv.per_invariant[q] = step_host[kStepInv0 + q];
+    r.sv.events.assign(1, pick->event);
+    std::vector<uint64_t> parents{((uint64_t)S.gid << 48) | pick->parent};
+    std::vector<std::vector<uint32_t>*> events{&r.sv.events};
+    return walk_chains("step invariants", parents, events);
+  }
+  // The step violation becomes the search's terminal (no exception or state invariant of the level
+  // outranks it: run_once): INVARIANT_VIOLATED at depth(P) + 1, index n_invariants + s, P's chain + E.
+  void report_step_terminal(SearchRun& r) {
+    r.end = DSL_INVARIANT_VIOLATED;
+    r.pred_index = dset.n_inv + r.sv.index;
+    r.term_depth = r.sv.depth;
+    trace_events = r.sv.events;
+    term_list.clear();
+    term_total = 0;
+    r.over = true;
+  }
+
   // Step: one k_level per shard with a frontier, bracketed by the timing events (a queued level
   // was launched with its queue).
   int launch_levels(SearchRun& r, const LevelPlan& p) {
     if (p.queued) return DSL_OK;
     DSL_TRY(enqueue_event_census(r));
+    DSL_TRY(enqueue_step_check(r));
     DSL_HIP(hipEventRecord(ev0, stream));
     for (auto& S : sh) {
       if (S.F == 0) continue;
@@ -2375,6 +2531,8 @@ struct BfsEngine : EngineBase {
                                  hipMemcpyDeviceToHost, stream));
         if (r.ev_pending)  // the event census's counts, with the level's own counters: no round trip of their own
           DSL_HIP(hipMemcpyAsync(ev_host, ev_dev, kEventWords * 8, hipMemcpyDeviceToHost, stream));
+        if (r.st_pending)  // ... and the step invariants' counters
+          DSL_HIP(hipMemcpyAsync(step_host, step_dev, kStepWords * 8, hipMemcpyDeviceToHost, stream));
         DSL_TRY(hsync());
         for (int l = 0; l < L; l++) {
           Shard& S = sh[l];
@@ -2476,6 +2634,8 @@ struct BfsEngine : EngineBase {
   // shard that holds it, the terminal's record (o.local_best).
   int fold_totals(SearchRun& r, const LevelPlan& p, LevelOutcome& o) {
     const int L = (int)sh.size();
+    // tests: the level that expands this depth counts as cut short by the deadline (no clock to wait on)
+    if (const char* cd = getenv("DSL_TEST_CUT_DEPTH")) o.level_tup |= r.depth == atoi(cd);
     for (int l = 0; l < (p.rep ? 1 : L); l++) {  // replicated: every shard has the same counts
       Shard& S = sh[l];
       o.sum.new_states += S.lc.new_states;
@@ -2575,8 +2735,15 @@ struct BfsEngine : EngineBase {
       // not a completed depth; a terminal it found is still reported (report_terminal)
       r.end = DSL_TIME_EXHAUSTED;
       r.over = true;
+      // ... and so is a step violation: its pass ran over the whole frontier before the level
+      if (r.st_pending && step_host[kStepViolating]) {
+        for (size_t l = 0; l < sh.size(); l++) sh[l].level_size.push_back(o.span[l]);
+        DSL_TRY(find_step_violation(r, r.depth));
+        report_step_terminal(r);
+      }
       return DSL_OK;
     }
+    const bool step_hit = r.st_pending && step_host[kStepViolating] != 0;
     r.depth++;
     if (sum.new_states)  // a completed level (single levels and queued ones alike)
       for (int w = 0; w < r.n_watch; w++) r.census[w].push_back(sh[0].lc.watch[w]);
@@ -2594,6 +2761,10 @@ struct BfsEngine : EngineBase {
     r.max_front = std::max(r.max_front, sum.rows);
     progress_depth = r.depth;
     for (size_t l = 0; l < sh.size(); l++) sh[l].level_size.push_back(o.span[l]);
+    // the step invariants: the edge row of a completed level, and the level's violation, found
+    // while the level's parents are still in S.cur
+    if (r.st_pending && !o.level_tup) r.step_edges.push_back(step_host[kStepJudged]);
+    if (step_hit) DSL_TRY(find_step_violation(r, r.depth - 1));
     // a wanted watch's first non-zero count in a completed level: its witness, while the level's
     // parents are still in S.cur (a level the deadline cut short is not enumerated)
     if (dset.watch_want && !o.level_tup && watch_wanted_hit(sh[0].lc, dset.watch_want)) {
@@ -2794,6 +2965,23 @@ struct BfsEngine : EngineBase {
     watch_census = std::move(run.census);
     event_census = std::move(run.events);
     watch_total = std::move(run.census_total);
+    // the step invariants: the edge rows, and the violation with P and X replayed on the host
+    step_edges = std::move(run.step_edges);
+    step_violation = StepViolation{};
+    if (run.sv.depth >= 0) {
+      StepViolation& v = step_violation;
+      v.index = run.sv.index;
+      v.depth = run.sv.depth;
+      v.edges = run.sv.edges;
+      std::memcpy(v.per_invariant, run.sv.per_invariant, sizeof(v.per_invariant));
+      v.trace.resize(run.sv.events.size());
+      const typename P::State xs = replay_events(run.sv.events, v.trace.data());
+      v.state.assign((const uint8_t*)&xs, (const uint8_t*)&xs + sizeof(init));
+      std::vector<dsl_event> scratch(run.sv.events.size());
+      const std::vector<uint32_t> prefix(run.sv.events.begin(), run.sv.events.end() - 1);
+      const typename P::State ps = replay_events(prefix, scratch.data());
+      v.parent.assign((const uint8_t*)&ps, (const uint8_t*)&ps + sizeof(init));
+    }
     // the witnesses: their events replayed on the host, as the terminal's are
     watch_witness.assign(run.n_watch, WatchWitness{});
     for (int w = 0; w < run.n_watch; w++) {
@@ -2831,8 +3019,13 @@ struct BfsEngine : EngineBase {
       DSL_TRY(check_level_errors(r, o));
       DSL_TRY(account_level(r, p, o));
       if (r.over) break;
-      if (o.enc != ~0ull)
+      // priority within the level: EXCEPTION > state INVARIANT > step INVARIANT > GOAL (o.enc's top
+      // bits are term_key's verdict)
+      const bool goal_only = o.enc != ~0ull && (int)(o.enc >> 62) + V_TERM_EXCEPTION == V_TERM_GOAL;
+      if (o.enc != ~0ull && !(r.sv.depth >= 0 && goal_only))
         DSL_TRY(report_terminal(r, p, o));
+      else if (r.sv.depth >= 0)
+        report_step_terminal(r);
       else
         DSL_TRY(advance_frontier(r, p, o));
     }

@@ -65,6 +65,30 @@ struct WatchList {
   int32_t n_pool = 0;
 };
 
+// The engine's step invariants (dsl_set_step_invariants): top-level predicates over an edge, with a
+// pool of their own.
+struct StepList {
+  const dsl_predicate* preds = nullptr;
+  int32_t n = 0;
+  const dsl_predicate* pool = nullptr;
+  int32_t n_pool = 0;
+};
+// DevPred::pad of a DSL_PRED_STEP_FIELD: DSL_CMP_* | kFieldRhsIsField | which side is read from the
+// successor (else from the parent)
+constexpr uint32_t kStepLhsNew = 16u, kStepRhsNew = 32u;
+// Device form of the step invariants: programs over ops [op0, op1) of DevSettings::ops, BEHIND
+// DevSettings::n_ops (no loop over ops[0, n_ops) sees a step op), their record conditions behind
+// the watches' in DevSettings::rec_conds. k_step_check alone takes it, in its own argument struct:
+// DevSettings keeps its layout and every other kernel its arguments.
+struct DevStep {
+  int32_t n_step = 0;
+  int32_t op0 = 0, op1 = 0;
+  int32_t n_sent = 0;     // DSL_PRED_STEP_SENT leaves; each has a bit of the step hit mask (DevPred::pad)
+  int32_t has_event = 0;  // some leaf is a DSL_PRED_STEP_EVENT: the event's class and node are needed
+  int32_t pad[3] = {0, 0, 0};
+  DevProg prog[DSL_MAX_STEP_INVARIANTS] = {};
+};
+
 // Device form of SearchSettings/TestSettings. The tri-state precedence of
 // TestSettings.shouldDeliver (TestSettings.java:224-245) is resolved on the host into a
 // boolean matrix deliver[from] bit `to`; timers into timer_mask bit a = deliverTimers(a).

@@ -244,9 +244,9 @@ static thread_local std::string g_last_error;
 void set_error(const std::string& msg) { g_last_error = msg; }
 
 int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out,
-                     const WatchList* watches) {
+                     const WatchList* watches, const StepList* steps, DevStep* step_out) {
   std::string why;
-  const int rc = resolve_settings(in, num_nodes, known, out, &why, watches);
+  const int rc = resolve_settings(in, num_nodes, known, out, &why, watches, steps, step_out);
   if (rc) set_error(why);
   return rc;
 }
@@ -591,6 +591,52 @@ int dsl_event_census(dsl_engine* e, int32_t level, dsl_event_count* cells, int32
   }
   static_assert(sizeof(dsl_event_count) == 32, "four 64-bit counts");
   std::memcpy(cells, rows[level].data(), dsl::EngineBase::kEventWords * 8);
+  return DSL_OK;
+}
+
+int dsl_set_step_invariants(dsl_engine* e, const dsl_predicate* preds, int32_t n, const dsl_predicate* pool,
+                            int32_t n_pool) {
+  if (!e) {
+    dsl::set_error("dsl_set_step_invariants: null engine");
+    return DSL_ERR_ARG;
+  }
+  return e->impl->set_step_invariants(preds, n, pool, n_pool);
+}
+
+int dsl_step_edges(dsl_engine* e, uint64_t* per_level, int32_t cap, int32_t* n_levels, uint64_t* total) {
+  if (n_levels) *n_levels = 0;
+  if (total) *total = 0;
+  if (!e || cap < 0 || (cap > 0 && !per_level)) return DSL_ERR_ARG;
+  const auto& rows = e->impl->step_edges;
+  uint64_t sum = 0;
+  for (size_t i = 0; i < rows.size(); i++) {
+    if ((int64_t)i < cap) per_level[i] = rows[i];
+    sum += rows[i];
+  }
+  if (n_levels) *n_levels = (int32_t)rows.size();
+  if (total) *total = sum;
+  return DSL_OK;
+}
+
+int dsl_step_violation(dsl_engine* e, int32_t* index, int32_t* depth, uint64_t* edges_violating,
+                       uint64_t per_invariant[DSL_MAX_STEP_INVARIANTS], dsl_event* trace, int32_t cap,
+                       int32_t* trace_len, uint8_t* parent_state, uint8_t* state, size_t len) {
+  if (index) *index = -1;
+  if (depth) *depth = -1;
+  if (edges_violating) *edges_violating = 0;
+  if (trace_len) *trace_len = 0;
+  if (per_invariant) std::memset(per_invariant, 0, sizeof(uint64_t) * DSL_MAX_STEP_INVARIANTS);
+  if (!e || cap < 0 || (cap > 0 && !trace)) return DSL_ERR_ARG;
+  const auto& v = e->impl->step_violation;
+  if (v.index < 0) return DSL_OK;  // none, or the last call was not a dsl_run
+  if (index) *index = v.index;
+  if (depth) *depth = v.depth;
+  if (edges_violating) *edges_violating = v.edges;
+  if (per_invariant) std::memcpy(per_invariant, v.per_invariant, sizeof(v.per_invariant));
+  for (int32_t i = 0; i < cap && i < (int32_t)v.trace.size(); i++) trace[i] = v.trace[i];
+  if (trace_len) *trace_len = (int32_t)v.trace.size();
+  if (parent_state && len == v.parent.size()) std::memcpy(parent_state, v.parent.data(), len);
+  if (state && len == v.state.size()) std::memcpy(state, v.state.data(), len);
   return DSL_OK;
 }
 

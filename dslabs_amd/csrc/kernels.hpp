@@ -1894,10 +1894,13 @@ __global__ void __launch_bounds__(kBlock) k_materialize(MaterializeArgs<P> a, ty
 // f and the view are those of a live STEP_OK successor that is not a no-op, {0, 0} and empty
 // otherwise. owner_filter: only the parents shard `me` of W owns were expanded (the first
 // hash-sharded level). watches: the row pre-scan also serves the watches' network leaves.
+// step (null: none): the step invariants' ops; visit's last argument is then the successor's step
+// hit mask (delta_step_hits, from the delta's registers), else 0.
 template <class P, class Visit>
 __device__ __forceinline__ void reexpand_level(const uint32_t* cur, const Fp* cur_fp, const SegTable& segs,
                                                bool owner_filter, int W, int me, bool incremental, bool watches,
-                                               const typename P::Params& prm, const DevSettings& set, Visit visit) {
+                                               const DevStep* step, const typename P::Params& prm,
+                                               const DevSettings& set, Visit visit) {
   constexpr int NW = Layout<P>::kWords;
   constexpr int PMAX = mat_per_max<P>();
   constexpr int NWV = kBlock / 64;
@@ -1935,6 +1938,7 @@ __device__ __forceinline__ void reexpand_level(const uint32_t* cur, const Fp* cu
       const bool live = t < total;
       int rc = STEP_NULL, k = 0, j = 0;
       bool noop = false;
+      uint32_t step_hits = 0;
       Fp pf{0, 0}, f{0, 0};
       NodeView view{nullptr, P::kNodeWords, -1, nullptr};
       if (live) {
@@ -1963,6 +1967,7 @@ __device__ __forceinline__ void reexpand_level(const uint32_t* cur, const Fp* cu
           if (!noop) {
             f = delta_fingerprint<P>(w, pf, d);
             view = successor_view<P>(w, d, row_hits, set, s_nodew, s_sends);
+            if (step) step_hits = delta_step_hits<P>(set, *step, d);
           }
         }
       }
@@ -1971,7 +1976,7 @@ __device__ __forceinline__ void reexpand_level(const uint32_t* cur, const Fp* cu
       view.base = wrows + j * NW;
       view.over = s_nodew + threadIdx.x * P::kNodeWords;
       if constexpr (NetPreds<P>::value) view.sends = s_sends + threadIdx.x * P::kMaxSends;
-      visit(live, rc, noop, p0 + (uint64_t)j, k, pf, f, view);
+      visit(live, rc, noop, p0 + (uint64_t)j, k, pf, f, view, step_hits);
     }
     __builtin_amdgcn_wave_barrier();  // the rows are overwritten by the next chunk's staging
   }
@@ -2011,8 +2016,8 @@ struct ListArgs {
 template <class P>
 __global__ void __launch_bounds__(kBlock) k_list_terminals(ListArgs<P> a, typename P::Params prm, DevSettings set) {
   reexpand_level<P>(
-      a.cur, a.cur_fp, a.segs, a.owner_filter != 0, a.W, a.me, a.incremental != 0, false, prm, set,
-      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp& pf, Fp f, const NodeView& view) {
+      a.cur, a.cur_fp, a.segs, a.owner_filter != 0, a.W, a.me, a.incremental != 0, false, nullptr, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp& pf, Fp f, const NodeView& view, uint32_t) {
         bool cand = false, exc = false;
         int tv = 0, tpi = -1;
         if (live && rc == STEP_OK && !noop) {
@@ -2089,8 +2094,8 @@ __global__ void __launch_bounds__(kBlock) k_watch_witness(WitnessArgs<P> a, type
 #pragma unroll
   for (int q = 0; q < DSL_MAX_WATCHES; q++) wkey[q] = find ? ~a.best[q] : ~0ull;
   reexpand_level<P>(
-      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, true, prm, set,
-      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp&, Fp f, const NodeView& view) {
+      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, true, nullptr, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp&, Fp f, const NodeView& view, uint32_t) {
         // a no-op is its parent: not new; exceptional successors are never counted
         uint32_t held = 0;
         if (live && rc == STEP_OK && !noop) held = eval_watches<P>(view, prm, set) & a.want;
@@ -2167,8 +2172,8 @@ __global__ void __launch_bounds__(kBlock) k_event_census(CensusArgs<P> a, typena
   for (int i = threadIdx.x; i < NCELL * 4; i += kBlock) s_hist[i] = 0;
   __syncthreads();
   reexpand_level<P>(
-      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, false, prm, set,
-      [&](bool live, int rc, bool noop, uint64_t, int k, const Fp&, Fp f, const NodeView& view) {
+      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, false, nullptr, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t, int k, const Fp&, Fp f, const NodeView& view, uint32_t) {
         int cell = -1;
         bool nop = false, exc = false, fresh = false;
         if (live && (rc == STEP_OK || rc == STEP_EXCEPTION)) {
@@ -2205,6 +2210,99 @@ __global__ void __launch_bounds__(kBlock) k_event_census(CensusArgs<P> a, typena
       const int cell = i >> 2, cls = cell / P::kNodes, to = cell - cls * P::kNodes;
       atomicAdd(&a.out[(size_t)(cls * DSL_EVENT_NODES + to) * 4 + (i & 3)], (unsigned long long)v);
     }
+  }
+}
+
+// ---- step invariants (dsl_set_step_invariants) -----------------------------------------------------
+// Runs BEFORE a level's k_level, in the event census's slot, over that level's frontier (in `cur`):
+// reexpand_level's fourth visitor. The visited table is neither read nor written -- an edge is
+// judged whatever became of its successor -- and no creator is read: every enabled event is
+// expanded, sleeping or not. Per live STEP_OK item that is not a no-op, each step program is
+// evaluated on the edge (eval_step_prog: the view holds the parent's and the successor's words, the
+// hit mask the records the step added; the event's class and node come from a second locate_event
+// on the parent row in LDS, only when a DSL_PRED_STEP_EVENT leaf exists).
+//   find = 0: counts, wave-reduced -- one __ballot + popcount per counter into wave-uniform
+//     accumulators with constant indices (edges judged, edges violating, one per step invariant) --
+//     and the wave's minimum parent fingerprint hi over its violating edges. At its exit a wave
+//     issues one global atomic add per counter (lane q adds counter q: one instruction) and one
+//     64-bit atomicMax of the minimum's complement, as k_watch_witness folds its keys.
+//   find = 1 (once per search, after the host read a non-zero violation count): a lane whose edge
+//     violates and whose parent's hi equals the minimum appends {parent row, event, lowest
+//     violated index, pf, f} through wave_reserve; the counter runs past `cap` (the host then runs
+//     this launch again at the exact size) and the host takes the smallest (pf.lo, event).
+// A kernel of its own: k_level and the other hot kernels do not move.
+struct StepRec {
+  uint64_t parent;  // index of the parent in the current frontier
+  uint32_t event;   // event index within the parent's enabled events
+  uint32_t index;   // the lowest violated step invariant
+  Fp pf, f;         // the parent's and the successor's fingerprints
+};
+constexpr int kStepJudged = 0, kStepViolating = 1, kStepInv0 = 2, kStepBest = kStepInv0 + DSL_MAX_STEP_INVARIANTS,
+              kStepOut = kStepBest + 1, kStepWords = 16;
+
+template <class P>
+struct StepArgs {
+  const uint32_t* cur;
+  const Fp* cur_fp;
+  SegTable segs;             // row ranges of the frontier; pb = parents per wave chunk, chunk0 in those chunks
+  int32_t incremental;
+  int32_t find;
+  DevStep step;
+  unsigned long long* ctr;   // kStepWords words: the counters, ~(minimum pf.hi) (0 = none), records appended
+  StepRec* out;
+  uint64_t cap;
+};
+
+template <class P>
+__global__ void __launch_bounds__(kBlock) k_step_check(StepArgs<P> a, typename P::Params prm, DevSettings set) {
+  const bool find = a.find != 0;
+  constexpr int NC = kStepInv0 + DSL_MAX_STEP_INVARIANTS;
+  uint32_t cnt[NC];  // wave-uniform, constant indices: registers (a wave's count of a level is below 2^32)
+#pragma unroll
+  for (int q = 0; q < NC; q++) cnt[q] = 0;
+  unsigned long long wkey = find ? ~a.ctr[kStepBest] : ~0ull;  // find = 0: the wave's minimum so far
+  bool seen = false;
+  reexpand_level<P>(
+      a.cur, a.cur_fp, a.segs, false, 1, 0, a.incremental != 0, false, &a.step, prm, set,
+      [&](bool live, int rc, bool noop, uint64_t parent, int k, const Fp& pf, Fp f, const NodeView& view, uint32_t hits) {
+        const bool judged = live && rc == STEP_OK && !noop;
+        uint32_t viol = 0;
+        if (judged) {
+          int cls = -1, to = -1;
+          if (a.step.has_event) step_event_cell<P>(view.base, locate_event<P>(view.base, prm, set, k), prm, &cls, &to);
+#pragma nounroll  // one copy of the predicate code; the trip count is wave-uniform
+          for (int s = 0; s < a.step.n_step; s++)
+            if (eval_step_prog<P>(set, a.step.prog[s], view, prm, hits, cls, to) != PV_TRUE) viol |= 1u << s;
+        }
+        if (!find) {
+          cnt[kStepJudged] += (uint32_t)__popcll(__ballot(judged));
+          const unsigned long long mv = __ballot(viol != 0u);
+          if (mv) {
+            cnt[kStepViolating] += (uint32_t)__popcll(mv);
+#pragma unroll
+            for (int q = 0; q < DSL_MAX_STEP_INVARIANTS; q++) cnt[kStepInv0 + q] += (uint32_t)__popcll(__ballot((viol >> q) & 1u));
+            // the wave's minimum key: a scalar walk over the (few) violating lanes
+            for (unsigned long long r = mv; r; r &= r - 1) {
+              const unsigned long long y = rl64(pf.hi, __ffsll((long long)r) - 1);
+              wkey = y < wkey ? y : wkey;
+            }
+            seen = true;
+          }
+        } else {
+          const bool hit = viol != 0u && pf.hi == wkey;
+          if (__ballot(hit)) {
+            const unsigned long long slot = wave_reserve(&a.ctr[kStepOut], hit);
+            if (hit && slot < a.cap) a.out[slot] = StepRec{parent, (uint32_t)k, (uint32_t)(__ffs((int)viol) - 1), pf, f};
+          }
+        }
+      });
+  if (!find) {  // lane q adds the wave's counter q: one atomic instruction per wave, and one for the key
+    const int lane = __lane_id();
+    uint32_t mine = 0;
+#pragma unroll
+    for (int q = 0; q < NC; q++) mine = lane == q ? cnt[q] : mine;
+    if (lane < NC && mine) atomicAdd(&a.ctr[lane], (unsigned long long)mine);
+    if (lane == 0 && seen) atomicMax(&a.ctr[kStepBest], ~wkey);
   }
 }
 

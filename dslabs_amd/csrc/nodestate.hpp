@@ -1098,4 +1098,136 @@ bool check_net_leaves(const DevSettings& d, std::string* why) {
   return true;
 }
 
+// ---- step invariants (dsl_set_step_invariants, include/dslabs_hip.h) ------------------------------
+// A step invariant is judged on an edge (P, E, X). The judge's delta view already holds both sides:
+// v.base + i * v.nw is node i of P, v.node(i) node i of X. Functions of their own, shared by
+// k_step_check and the host walk (tests/hostcheck/stepcheck.cpp): eval_prog, which every
+// k_level<P, *, true> compiles, has no branch for them.
+DSL_HD uint32_t step_field_read(const NodeView& v, uint32_t desc, bool from_new) {
+  const int bit = DSL_FIELD_BIT(desc), width = DSL_FIELD_WIDTH(desc), node = DSL_FIELD_NODE(desc);
+  const uint32_t* w = from_new ? v.node(node) : v.base + node * v.nw;
+  const uint32_t x = w[bit >> 5] >> (bit & 31);
+  return width >= 32 ? x : x & ((1u << width) - 1u);  // no 1u << 32
+}
+DSL_HD int eval_step_field_leaf(const DevPred& pr, const NodeView& v) {
+  const uint32_t a = step_field_read(v, (uint32_t)pr.arg0, (pr.pad & kStepLhsNew) != 0u);
+  const uint32_t b = (pr.pad & kFieldRhsIsField) ? step_field_read(v, (uint32_t)pr.arg1, (pr.pad & kStepRhsNew) != 0u)
+                                                 : (uint32_t)pr.arg1;
+  const uint32_t c = pr.pad & 7u;  // DSL_CMP_*, as eval_field_leaf
+  const bool base = (c >> 1) == 0 ? a == b : (c >> 1) == 1 ? a < b : a <= b;
+  return (base != (bool)(c & 1u)) ? PV_TRUE : PV_FALSE;
+}
+// The step hit mask of an edge from its delta: bit i = a KEPT send (a record new to the parent's
+// set) satisfies DSL_PRED_STEP_SENT leaf i (DevPred::pad). Over the step ops only; the send list is
+// read through compile-time indices, as delta_net_hits reads it.
+template <class P>
+DSL_HD uint32_t delta_step_hits(const DevSettings& set, const DevStep& step, const Delta<P>& d) {
+  uint32_t hits = 0;
+  if (d.keep == 0u || step.n_sent == 0) return 0u;
+  for (int i = step.op0; i < step.op1; i++) {
+    const DevPred& op = set.ops[i];
+    if (op.id != DSL_PRED_STEP_SENT) continue;
+    uint32_t alive = d.keep;
+    for (int c = 0; c < op.arg1; c++) {
+      const DevRecCond rc = set.rec_conds[op.arg0 + c];
+#pragma unroll
+      for (int q = 0; q < P::kMaxSends; q++)
+        if (((alive >> q) & 1u) && !rec_cond_holds<typename P::Rec>(rc, d.out.r[q])) alive &= ~(1u << q);
+    }
+    if (alive) hits |= 1u << op.pad;
+  }
+  return hits;
+}
+// StatePredicate.test of a step program on the edge whose successor `v` views: eval_prog's stack
+// machine and three-valued rules with the step leaves added. hits: delta_step_hits; cls / to: the
+// event's handler class and node (read only by a DSL_PRED_STEP_EVENT leaf). DSL_PRED_FIELD and the
+// protocol's named leaves are evaluated on the successor.
+template <class P>
+DSL_HD int eval_step_prog(const DevSettings& set, DevProg g, const NodeView& v0, const typename P::Params& prm,
+                          uint32_t hits, int cls, int to) {
+  NodeView v = v0;
+  if constexpr (NetPreds<P>::value) {  // the successor's network() includes the dropped set, as in judge_view
+    v.dropped = set.dropped();
+    v.ndropped = set.n_dropped;
+  }
+  uint32_t st = 0;
+  for (int i = 0; i < g.len; i++) {
+    const DevPred& op = set.ops[g.start + i];
+    int x;
+    if (op.id == kOpAnd || op.id == kOpOr) {
+      const int b = (int)(st & 3u);
+      st >>= 2;
+      const int a = (int)(st & 3u);
+      st >>= 2;
+      x = a == PV_THREW ? PV_THREW : op.id == kOpAnd ? (a == PV_FALSE ? PV_FALSE : b) : (a == PV_TRUE ? PV_TRUE : b);
+    } else if (op.id == kOpNot) {
+      const int a = (int)(st & 3u);
+      st >>= 2;
+      x = a == PV_THREW ? PV_THREW : !a;
+    } else {
+      x = op.id == DSL_PRED_STEP_FIELD   ? eval_step_field_leaf(op, v)
+          : op.id == DSL_PRED_STEP_SENT  ? (((hits >> op.pad) & 1u) ? PV_TRUE : PV_FALSE)
+          : op.id == DSL_PRED_STEP_EVENT ? (((op.arg0 < 0 || op.arg0 == cls) && (op.arg1 < 0 || op.arg1 == to)) ? PV_TRUE : PV_FALSE)
+          : op.id == DSL_PRED_FIELD      ? eval_field_leaf(op, v)
+                                         : P::eval(op, v, prm);
+      if (x != PV_THREW && op.negate) x = !x;
+    }
+    st = (st << 2) | (uint32_t)x;
+  }
+  return (int)(st & 3u);
+}
+// The handler class and node of located event e of parent row w, as the event census classifies it
+// (an event the no-op filters would skip has its real class).
+template <class P>
+DSL_HD void step_event_cell(const uint32_t* w, int e, const typename P::Params& prm, int* cls, int* to) {
+  if (e >= 0) {
+    const auto r = Net<P>::at(w, e);
+    *cls = P::msg_class(r);
+    *to = P::rec_to(r);
+  } else {
+    *to = (-1 - e) >> 8;
+    *cls = Classes<P>::kTimer0 + TimerClasses<P>::of(*to, prm);
+  }
+}
+// The checks of the step ops that need the protocol (resolve_settings made the rest; the loops of
+// check_field_leaves / check_net_leaves / set_pred_reads end at n_ops and never see a step op):
+// fields inside the node, conditions inside the record, the class among the protocol's; the read
+// set of a named leaf, which its P::eval may consult.
+template <class P>
+bool check_step_leaves(DevSettings& d, const DevStep& step, const typename P::Params& prm, std::string* why) {
+  for (int i = step.op0; i < step.op1; i++) {
+    DevPred& op = d.ops[i];
+    if (op.id == DSL_PRED_FIELD || op.id == DSL_PRED_STEP_FIELD) {
+      const uint32_t descs[2] = {(uint32_t)op.arg0, (uint32_t)op.arg1};
+      for (int k = 0; k < ((op.pad & kFieldRhsIsField) ? 2 : 1); k++) {
+        const int bit = DSL_FIELD_BIT(descs[k]), width = DSL_FIELD_WIDTH(descs[k]);
+        if (bit + width > 32 * P::kNodeWords) {
+          *why = std::string("field predicate: ") + (k ? "right" : "left") + " operand (node " +
+                 std::to_string(DSL_FIELD_NODE(descs[k])) + ", bit " + std::to_string(bit) + ", width " +
+                 std::to_string(width) + "): beyond the node's " + std::to_string(32 * P::kNodeWords) + " bits";
+          return false;
+        }
+      }
+    } else if (op.id == DSL_PRED_STEP_SENT) {
+      for (int c = 0; c < op.arg1; c++) {
+        const DevRecCond& rc = d.rec_conds[op.arg0 + c];
+        if (rc.bit + rc.width > 8 * (int)sizeof(typename P::Rec)) {
+          *why = "network predicate: condition " + std::to_string(c) + " (bit " + std::to_string(rc.bit) + ", width " +
+                 std::to_string(rc.width) + "): beyond the record's " + std::to_string(8 * sizeof(typename P::Rec)) + " bits";
+          return false;
+        }
+      }
+    } else if (op.id == DSL_PRED_STEP_EVENT) {
+      if (op.arg0 >= Classes<P>::kSkip) {
+        *why = "step event leaf: class " + std::to_string(op.arg0) + " outside the protocol's " +
+               std::to_string((int)Classes<P>::kSkip) + " handler classes";
+        return false;
+      }
+    } else if (op.id > 0) {
+      op.reads = P::pred_reads(op, prm);
+    }
+  }
+  return true;
+}
+
 }  // namespace dsl

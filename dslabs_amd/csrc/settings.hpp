@@ -13,9 +13,17 @@ namespace dsl {
 // TestSettings.deliverTimers(a): per-address override else the global flag (:87-89).
 // watches (optional): compiled behind the settings' own predicates into the same ops[] and
 // rec_conds[], with the same checks; a failure leaves *out untouched.
+// steps (optional, with step_out): the step invariants (dsl_set_step_invariants), compiled after
+// everything else into ops[n_ops, ...) and rec_conds behind the watches' -- n_ops, n_net, flat,
+// watch_net and the read sets are what they are without them, so no loop over ops[0, n_ops) ever
+// sees a step op -- and described in *step_out. A failure leaves *out and *step_out untouched.
 inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)(int), DevSettings* out,
-                            std::string* why_out, const WatchList* watches = nullptr) {
+                            std::string* why_out, const WatchList* watches = nullptr, const StepList* steps = nullptr,
+                            DevStep* step_out = nullptr) {
   DevSettings d{};
+  DevStep ds{};
+  bool in_step = false;              // compiling a step invariant: the step leaves are legal, DSL_PRED_NET is not
+  const char* list_name = "invariants";  // the list being compiled, for the refusals' text
   if (num_nodes > DSL_MAX_NODES) return *why_out = "too many nodes", DSL_ERR_ARG;
   if (in.do_checks < DSL_CHECKS_NONE || in.do_checks > DSL_CHECKS_ALL || in.check_sample < 0)
     return *why_out = "do_checks must be DSL_CHECKS_NONE / _ERRORS / _ALL and check_sample >= 0", DSL_ERR_ARG;
@@ -72,13 +80,38 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
       if (p.negate && !push_op(kOpNot)) return false;
       return true;
     }
-    if (p.pred_id == DSL_PRED_FIELD) {
+    if (p.pred_id == DSL_PRED_STEP_FIELD || p.pred_id == DSL_PRED_STEP_SENT || p.pred_id == DSL_PRED_STEP_EVENT) {
+      const char* leaf = p.pred_id == DSL_PRED_STEP_FIELD ? "DSL_PRED_STEP_FIELD"
+                         : p.pred_id == DSL_PRED_STEP_SENT ? "DSL_PRED_STEP_SENT" : "DSL_PRED_STEP_EVENT";
+      if (!in_step)
+        return why = std::string("step leaf ") + leaf + " in the " + list_name +
+                     ": a step leaf is legal only in a step invariant (dsl_set_step_invariants)", false;
+    }
+    if (in_step && p.pred_id == DSL_PRED_NET)
+      return why = "DSL_PRED_NET in a step invariant is not supported: use DSL_PRED_STEP_SENT for the records the "
+                   "step added", false;
+    if (p.pred_id == DSL_PRED_STEP_EVENT) {
+      // the class is checked against the protocol's classes in check_step_leaves<P>
+      if (p.arg0 < -1 || p.arg0 > 15) return why = "step event leaf: class " + std::to_string(p.arg0) + " out of range", false;
+      if (p.arg1 < -1 || p.arg1 >= num_nodes)
+        return why = "step event leaf: node " + std::to_string(p.arg1) + " outside -1.." + std::to_string(num_nodes - 1), false;
+      if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
+      d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, (int32_t)p.arg0, (int32_t)p.arg1, 0u, 0u};
+      ds.has_event = 1;
+      if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
+      return true;
+    }
+    if (p.pred_id == DSL_PRED_FIELD || p.pred_id == DSL_PRED_STEP_FIELD) {
       // the generic field leaf: every protocol's (the judge evaluates it, not P::eval); packed
       // into the DevPred's 96 argument bits. The one check that needs the protocol's words per
       // node is check_field_leaves<P> (nodestate.hpp), where P is known.
       const uint64_t a0 = (uint64_t)p.arg0, a1 = (uint64_t)p.arg1;
       const int cmp = DSL_FIELD_ARG0_CMP(a0), rhs_field = DSL_FIELD_ARG0_RHS_IS_FIELD(a0);
-      if (a0 >> 36) return why = "field predicate: arg0 has bits set above the descriptor, comparison and operand kind", false;
+      const bool stepf = p.pred_id == DSL_PRED_STEP_FIELD;
+      if (a0 >> (stepf ? 38 : 36))
+        return why = "field predicate: arg0 has bits set above the descriptor, comparison and operand kind", false;
+      if (stepf && DSL_STEP_ARG0_RHS_NEW(a0) && !rhs_field)
+        return why = "field predicate: arg0 bit 37 (right operand from the successor) without a right field", false;
       if (cmp > DSL_CMP_GT) return why = "field predicate: unknown comparison " + std::to_string(cmp), false;
       if (a1 >> 32) return why = "field predicate: arg1 does not fit in 32 unsigned bits", false;
       auto bad_desc = [&](uint32_t desc, const char* side) {
@@ -95,11 +128,14 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
       if (rhs_field && bad_desc((uint32_t)a1, "right")) return false;
       if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
       d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, (int32_t)DSL_FIELD_ARG0_DESC(a0), (int32_t)(uint32_t)a1, 0u,
-                                 (uint32_t)cmp | (rhs_field ? kFieldRhsIsField : 0u)};
+                                 (uint32_t)cmp | (rhs_field ? kFieldRhsIsField : 0u) |
+                                     (stepf && DSL_STEP_ARG0_LHS_NEW(a0) ? kStepLhsNew : 0u) |
+                                     (stepf && DSL_STEP_ARG0_RHS_NEW(a0) ? kStepRhsNew : 0u)};
       if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
       return true;
     }
-    if (p.pred_id == DSL_PRED_NET) {
+    if (p.pred_id == DSL_PRED_NET || p.pred_id == DSL_PRED_STEP_SENT) {
+      // (DSL_PRED_STEP_SENT: the same pool encoding; its ordinal is among the step leaves, ds.n_sent)
       // the generic network leaf: every protocol's. Its conditions (consecutive DSL_PRED_REC_COND
       // pool entries) go into DevSettings::rec_conds; the DevPred keeps (first, count) and the
       // leaf's ordinal. bit + width against the record's size is check_net_leaves<P>'s.
@@ -125,7 +161,8 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
         d.rec_conds[n_rec++] = DevRecCond{(uint16_t)DSL_REC_ARG0_BIT(a0), (uint8_t)width, (uint8_t)cmp, (uint32_t)a1};
       }
       if (d.n_ops >= kMaxProgOps) return why = "predicate programs too long", false;
-      d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, first, (int32_t)p.arg1, 0u, (uint32_t)d.n_net++};
+      d.ops[d.n_ops++] = DevPred{p.pred_id, p.negate, first, (int32_t)p.arg1, 0u,
+                                 (uint32_t)(p.pred_id == DSL_PRED_NET ? d.n_net++ : ds.n_sent++)};
       if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
       return true;
     }
@@ -138,7 +175,8 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
     if (++*sp > kMaxProgStack) return why = "predicate too wide", false;
     return true;
   };
-  auto compile = [&](const dsl_predicate* src, int n, DevProg* dst) {
+  auto compile = [&](const dsl_predicate* src, int n, DevProg* dst, const char* name) {
+    list_name = name;
     for (int i = 0; i < n; i++) {
       const int start = d.n_ops;
       int sp = 0;
@@ -147,8 +185,8 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
     }
     return true;
   };
-  if (!compile(in.invariants, d.n_inv, d.inv) || !compile(in.goals, d.n_goal, d.goal) ||
-      !compile(in.prunes, d.n_prune, d.prune)) {
+  if (!compile(in.invariants, d.n_inv, d.inv, "invariants") || !compile(in.goals, d.n_goal, d.goal, "goals") ||
+      !compile(in.prunes, d.n_prune, d.prune, "prunes")) {
     *why_out = why;
     return why.rfind("predicate not supported", 0) == 0 ? DSL_ERR_UNKNOWN_PREDICATE : DSL_ERR_ARG;
   }
@@ -163,14 +201,36 @@ inline int resolve_settings(const dsl_settings& in, int num_nodes, bool (*known)
     pool = watches->pool;
     n_pool = watches->n_pool;
     const int net0 = d.n_net;
-    if (!compile(watches->watches, watches->n, d.watch)) {
+    if (!compile(watches->watches, watches->n, d.watch, "watches")) {
       *why_out = why;
       return why.rfind("predicate not supported", 0) == 0 ? DSL_ERR_UNKNOWN_PREDICATE : DSL_ERR_ARG;
     }
     d.n_watch = watches->n;
     d.watch_net = d.n_net > net0 ? 1 : 0;
   }
+  if (steps && steps->n != 0) {
+    if (steps->n < 0 || steps->n > DSL_MAX_STEP_INVARIANTS)
+      return *why_out = "step invariants: " + std::to_string(steps->n) + ", outside 0.." +
+                        std::to_string(DSL_MAX_STEP_INVARIANTS), DSL_ERR_ARG;
+    if (!step_out || !steps->preds || steps->n_pool < 0 || steps->n_pool > DSL_MAX_POOL || (steps->n_pool > 0 && !steps->pool))
+      return *why_out = "step invariants: predicate counts out of range", DSL_ERR_ARG;
+    pool = steps->pool;
+    n_pool = steps->n_pool;
+    const int ops0 = d.n_ops;
+    in_step = true;
+    const bool ok = compile(steps->preds, steps->n, ds.prog, "step invariants");
+    in_step = false;
+    if (!ok) {
+      *why_out = why;
+      return why.rfind("predicate not supported", 0) == 0 ? DSL_ERR_UNKNOWN_PREDICATE : DSL_ERR_ARG;
+    }
+    ds.n_step = steps->n;
+    ds.op0 = ops0;
+    ds.op1 = d.n_ops;
+    d.n_ops = ops0;  // the step ops stay behind n_ops
+  }
   *out = d;
+  if (step_out) *step_out = ds;
   return DSL_OK;
 }
 

@@ -65,6 +65,25 @@ class Protocol:
             self.__dict__["_event_classes"] = cached
         return list(cached)
 
+    def delivered(self, cls=None, to=None):
+        """A step leaf (SearchSettings.addStepInvariant): the step's event is of handler class
+        ``cls`` (a name of ``event_classes()`` or its index; None = any) and is delivered to ``to``
+        (an address; None = any node; a timer's node is its own)."""
+        from .search import PRED_STEP_EVENT, StatePredicate
+        ci = -1
+        if cls is not None:
+            names = [n for n, _ in self.event_classes()]
+            ci = cls if isinstance(cls, int) and not isinstance(cls, bool) else names.index(cls) if cls in names else None
+            if ci is None or not 0 <= ci < len(names):
+                raise ValueError(f"delivered: unknown handler class {cls!r} (event_classes(): {names})")
+        ti = -1
+        if to is not None:
+            ti = self.address_index(to)
+            if not 0 <= ti < len(self.addresses):
+                raise ValueError(f"unknown address {to!r}")
+        what = "any event" if cls is None else str(cls if isinstance(cls, str) else self.event_classes()[ci][0])
+        return StatePredicate(f"delivered {what}" + (f" to {self.addresses[ti]}" if ti >= 0 else ""), PRED_STEP_EVENT, ci, ti)
+
     def initial_state(self) -> SearchState:
         return SearchState(self)
 

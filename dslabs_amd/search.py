@@ -88,6 +88,26 @@ def rec_arg0_decode(arg0: int) -> tuple:
     return arg0 & 0xFFFF, (arg0 >> 16) & 0x3F, (arg0 >> 32) & 7
 
 
+# The step leaves (DSL_PRED_STEP_*, include/dslabs_hip.h): legal only in a step invariant
+PRED_STEP_FIELD = 953
+PRED_STEP_SENT = 954
+PRED_STEP_EVENT = 955
+STEP_LHS_NEW_BIT, STEP_RHS_NEW_BIT = 36, 37
+_STEP_LEAVES = (PRED_STEP_FIELD, PRED_STEP_SENT, PRED_STEP_EVENT)
+
+
+def step_field_arg0(desc: int, cmp: int, rhs_is_field: bool, lhs_new: bool, rhs_new: bool) -> int:
+    """DSL_STEP_FIELD_ARG0"""
+    return field_arg0(desc, cmp, rhs_is_field) | (1 << STEP_LHS_NEW_BIT if lhs_new else 0) | \
+        (1 << STEP_RHS_NEW_BIT if rhs_new else 0)
+
+
+def step_field_arg0_decode(arg0: int) -> tuple:
+    """(descriptor, comparison, rhs_is_field, lhs_new, rhs_new): DSL_FIELD_ARG0_* / DSL_STEP_ARG0_*"""
+    return field_arg0_decode(arg0 & ((1 << 36) - 1)) + (bool((arg0 >> STEP_LHS_NEW_BIT) & 1),
+                                                       bool((arg0 >> STEP_RHS_NEW_BIT) & 1))
+
+
 class StatePredicate:
     """A named state predicate evaluated on the device (StatePredicate.java).
 
@@ -130,11 +150,11 @@ class StatePredicate:
     def _encode(self, state: "SearchState", pool: list) -> _lib.dsl_predicate:
         """The C ABI form; a combinator's operands and a network leaf's conditions are appended to
         ``pool`` (dsl_settings.pool)."""
-        if self.pred_id == PRED_NET:
+        if self.pred_id in (PRED_NET, PRED_STEP_SENT):
             first = len(pool)
             for c in self.conds:  # consecutive pool entries
                 pool.append(_lib.dsl_predicate(PRED_REC_COND, 0, rec_arg0(c.bit, c.width, c.cmp), c.const))
-            return _lib.dsl_predicate(PRED_NET, 1 if self.negated else 0, first, len(self.conds))
+            return _lib.dsl_predicate(self.pred_id, 1 if self.negated else 0, first, len(self.conds))
         if self.operands:
             idx = []
             for op in self.operands:
@@ -184,6 +204,9 @@ class FieldRef:
         return FieldRef(self.protocol, self.node, self.bit + lo, width, f"{self.name}[{lo}:{lo + width}]")
 
     def _cmp(self, cmp: int, other) -> StatePredicate:
+        if isinstance(other, StepFieldRef):
+            raise TypeError(f"{self.name}: in a step predicate both sides name their state: wrap this field in "
+                            f"old(...) or new(...) to compare it with {other.name}")
         if isinstance(other, FieldRef):
             if other.protocol is not self.protocol:
                 raise ValueError(f"{self.name} and {other.name} belong to different protocol objects")
@@ -219,6 +242,71 @@ class FieldRef:
 
     def __repr__(self) -> str:
         return self.name
+
+
+class StepFieldRef:
+    """``old(ref)`` / ``new(ref)``: a FieldRef read from the parent or from the successor of a step.
+    Comparing it with an int, ``old(..)`` or ``new(..)`` gives a step leaf (DSL_PRED_STEP_FIELD) for
+    ``SearchSettings.addStepInvariant``; a bare FieldRef on the other side is an error."""
+
+    def __init__(self, ref: FieldRef, is_new: bool):
+        if not isinstance(ref, FieldRef):
+            raise TypeError(f"{'new' if is_new else 'old'}(...) wraps a FieldRef, not {type(ref).__name__}")
+        self.ref, self.is_new = ref, bool(is_new)
+        self.name = f"{'new' if is_new else 'old'}({ref.name})"
+
+    def bits(self, lo: int, width: int) -> "StepFieldRef":
+        return StepFieldRef(self.ref.bits(lo, width), self.is_new)
+
+    def _cmp(self, cmp: int, other) -> "StatePredicate":
+        if isinstance(other, StepFieldRef):
+            if other.ref.protocol is not self.ref.protocol:
+                raise ValueError(f"{self.name} and {other.name} belong to different protocol objects")
+            return StatePredicate(f"{self.name} {_CMP_TEXT[cmp]} {other.name}", PRED_STEP_FIELD,
+                                  step_field_arg0(self.ref.desc(), cmp, True, self.is_new, other.is_new), other.ref.desc())
+        if isinstance(other, FieldRef):
+            raise TypeError(f"{self.name}: in a step predicate both sides name their state: wrap {other.name} in "
+                            "old(...) or new(...)")
+        if isinstance(other, bool) or not isinstance(other, int):
+            raise TypeError(f"{self.name}: compare with an int, old(...) or new(...), not {type(other).__name__}")
+        if other < 0 or other >= 1 << 32:
+            raise ValueError(f"{self.name}: constant {other} does not fit in 32 unsigned bits")
+        return StatePredicate(f"{self.name} {_CMP_TEXT[cmp]} {other}", PRED_STEP_FIELD,
+                              step_field_arg0(self.ref.desc(), cmp, False, self.is_new, False), other)
+
+    def eq(self, other):
+        return self._cmp(CMP_EQ, other)
+
+    def ne(self, other):
+        return self._cmp(CMP_NE, other)
+
+    def lt(self, other):
+        return self._cmp(CMP_LT, other)
+
+    def le(self, other):
+        return self._cmp(CMP_LE, other)
+
+    def gt(self, other):
+        return self._cmp(CMP_GT, other)
+
+    def ge(self, other):
+        return self._cmp(CMP_GE, other)
+
+    __eq__, __ne__, __lt__, __le__, __gt__, __ge__ = eq, ne, lt, le, gt, ge
+    __hash__ = object.__hash__
+
+    def __repr__(self) -> str:
+        return self.name
+
+
+def old(ref: FieldRef) -> StepFieldRef:
+    """``ref`` as the step's parent state holds it."""
+    return StepFieldRef(ref, False)
+
+
+def new(ref: FieldRef) -> StepFieldRef:
+    """``ref`` as the step's successor holds it."""
+    return StepFieldRef(ref, True)
 
 
 def make_field_ref(protocol, address, bit: int, width: int, name: str) -> FieldRef:
@@ -329,6 +417,13 @@ class MessagePattern:
         _check_rec_field(f"{self.label}.bits[{bit}:{bit + width}]", bit, width, self.rec_bits)
         return RecFieldRef(bit, width, f"bits[{bit}:{bit + width}]")
 
+    def sent(self, *conds: RecCond) -> StatePredicate:
+        """A step leaf (SearchSettings.addStepInvariant): the step ADDED to the network a message of
+        this pattern satisfying every condition (DSL_PRED_STEP_SENT). The network is a set: a
+        message the parent already holds is not added by sending it again."""
+        p = self.where(*conds)
+        return StatePredicate("sent" + p.name[len("contains"):], PRED_STEP_SENT, conds=p.conds)
+
     def where(self, *conds: RecCond) -> StatePredicate:
         for c in conds:
             if not isinstance(c, RecCond):
@@ -412,6 +507,40 @@ class PredicateResult:
 _NO_WATCHES = (b"", None, 0, None, 0)  # SearchSettings._encode_watches of a search without watches
 
 
+def _step_leaf_in(p: StatePredicate) -> Optional[StatePredicate]:
+    """The first step leaf of a predicate tree, or None."""
+    if p.pred_id in _STEP_LEAVES:
+        return p
+    for o in p.operands:
+        f = _step_leaf_in(o)
+        if f is not None:
+            return f
+    return None
+
+
+def _no_step_leaf(p: StatePredicate, what: str) -> None:
+    f = _step_leaf_in(p)
+    if f is not None:
+        raise ValueError(f"{what}: {f.name!r} is a step leaf: it is legal only in a step invariant (addStepInvariant)")
+
+
+def _has_pred(p: StatePredicate, pred_id: int) -> bool:
+    return p.pred_id == pred_id or any(_has_pred(o, pred_id) for o in p.operands)
+
+
+@dataclass
+class StepViolation:
+    """SearchResults.stepViolation(): the reported violating edge of a search with step invariants."""
+    index: int                 # the lowest violated step invariant of the edge
+    name: str
+    depth: int                 # depth(parent) + 1
+    parent: "SearchState"
+    state: "SearchState"
+    event: str                 # the edge's event, decoded
+    edges: int                 # the level's violating edges
+    perInvariant: List[int]    # ... per step invariant (an edge counts for every one it violates)
+
+
 class SearchSettings:
     """SearchSettings + TestSettings (fluent setters return self)."""
 
@@ -449,6 +578,48 @@ class SearchSettings:
         # the event census (dsl_set_event_census): per level, the events applied per handler class
         # and destination node (SearchResults.eventCensus()); it changes nothing else
         self._event_census = False
+        # step invariants (dsl_set_step_invariants): predicates over an edge (parent, event, successor)
+        self._step_invariants: List[StatePredicate] = []
+
+    def addStepInvariant(self, p: StatePredicate) -> "SearchSettings":
+        """A predicate every step (parent, event, successor) of the search must satisfy, built from
+        ``old(ref) / new(ref)`` comparisons, ``MessagePattern.sent``, ``Protocol.delivered``, field
+        comparisons and named predicates (both on the successor) and the combinators; at most 8. A
+        step that changes nothing is exempt. The search ends INVARIANT_VIOLATED at the first level
+        with a violated step (SearchResults.stepViolation). BFS on one shard."""
+        if len(self._step_invariants) >= _lib.DSL_MAX_STEP_INVARIANTS:
+            raise ValueError(f"too many step invariants: at most {_lib.DSL_MAX_STEP_INVARIANTS} in one search")
+        if _has_pred(p, PRED_NET):
+            raise ValueError(f"addStepInvariant: {p.name!r} holds a message predicate over the whole network "
+                             "(MessagePattern.where), which a step invariant does not support: use .sent(...)")
+        self._step_invariants.append(p)
+        return self
+
+    def clearStepInvariants(self) -> "SearchSettings":
+        self._step_invariants.clear()
+        return self
+
+    def stepInvariants(self) -> List[StatePredicate]:
+        return list(self._step_invariants)
+
+    def _encode_steps(self, state: "SearchState") -> tuple:
+        """``(key, preds, n, pool, n_pool)`` as dsl_set_step_invariants takes them (see _encode_watches)."""
+        if not self._step_invariants:
+            return _NO_WATCHES
+        sig = (state.protocol, tuple(self._step_invariants))
+        cached = self.__dict__.get("_step_cache")
+        if cached is not None and cached[0] == sig:
+            return cached[1]
+        pool: list = []
+        preds = [p._encode(state, pool) for p in self._step_invariants]
+        if len(pool) > _lib.DSL_MAX_POOL:
+            raise ValueError(f"too many combinator operands and message conditions in the step invariants: {len(pool)} "
+                             f"pool entries, at most {_lib.DSL_MAX_POOL}")
+        w = (_lib.dsl_predicate * _lib.DSL_MAX_STEP_INVARIANTS)(*preds)
+        pl = (_lib.dsl_predicate * _lib.DSL_MAX_POOL)(*pool)
+        enc = (bytes(w) + bytes(pl), w, len(preds), pl, len(pool))
+        self.__dict__["_step_cache"] = (sig, enc)
+        return enc
 
     def eventCensus(self, on: bool = True) -> "SearchSettings":
         """Counts, per expanded level, the events applied per (handler class, destination node):
@@ -466,6 +637,7 @@ class SearchSettings:
         (SearchResults.watchWitness): what a goal search's goalMatchingState() gives."""
         if len(self._watches) >= _lib.DSL_MAX_WATCHES:
             raise ValueError(f"too many watches: at most {_lib.DSL_MAX_WATCHES} in one search")
+        _no_step_leaf(p, "addWatch")
         self._watches.append(p)
         self._witness.append(bool(witness))
         return self
@@ -522,6 +694,7 @@ class SearchSettings:
 
     # TestSettings -------------------------------------------------------------------------
     def addInvariant(self, p: StatePredicate) -> "SearchSettings":
+        _no_step_leaf(p, "addInvariant")
         self._invariants.append(p)
         return self
 
@@ -600,6 +773,7 @@ class SearchSettings:
         return self._max_depth >= 0
 
     def addGoal(self, p: StatePredicate) -> "SearchSettings":
+        _no_step_leaf(p, "addGoal")
         self._goals.append(p)
         return self
 
@@ -611,6 +785,7 @@ class SearchSettings:
         return list(self._goals)
 
     def addPrune(self, p: StatePredicate) -> "SearchSettings":
+        _no_step_leaf(p, "addPrune")
         self._prunes.append(p)
         return self
 
@@ -624,7 +799,7 @@ class SearchSettings:
     def clone(self) -> "SearchSettings":
         s = SearchSettings()
         s.__dict__.update({k: (v.copy() if isinstance(v, (list, dict)) else v) for k, v in self.__dict__.items()
-                           if k not in ("_enc_cache", "_watch_cache")})
+                           if k not in ("_enc_cache", "_watch_cache", "_step_cache")})
         return s
 
     # encoding -------------------------------------------------------------------------------
@@ -817,6 +992,8 @@ class SearchResults:
         self._watch_counts: List[List[int]] = []
         self._watch_totals: List[int] = []
         self._witnesses: List[Optional[SearchState]] = []
+        self._step_edges: List[int] = []
+        self._step_violation: Optional[StepViolation] = None
         self._event_rows: list = []       # [level][cls][to] = (events, noops, exceptions, fresh)
         self._event_classes: list = []    # [(name, is_timer)] of the protocol
         self._event_addresses: list = []
@@ -899,6 +1076,17 @@ class SearchResults:
         if not 0 <= i < n:
             raise ValueError(f"watchWitness: watch {i} of {n}")
         return self._witnesses[i] if i < len(self._witnesses) else None
+
+    # step invariants (SearchSettings.addStepInvariant) -----------------------------------------
+    def stepEdges(self) -> List[int]:
+        """Edges judged per completed level (index i: the parents of depth ``initial_depth + i``).
+        Empty without step invariants, and after a DFS or a replay."""
+        return list(self._step_edges)
+
+    def stepViolation(self) -> Optional[StepViolation]:
+        """The reported violating edge, or None. It is there also when an exception or a state
+        invariant of the same level outranked it as the search's terminal."""
+        return self._step_violation
 
     # the event census (SearchSettings.eventCensus) ----------------------------------------------
     def eventRows(self) -> list:
@@ -1007,6 +1195,13 @@ class Engine:
             check(lib.dsl_set_watches(self.handle, None, 0, None, 0), "dsl_set_watches")
             self._set_watch_key = held = b""
             self._set_witness_mask = 0  # dsl_set_watches resets it
+        # the step invariants: as the watches, told only when they differ from what the engine holds,
+        # the old ones leaving before the new settings arrive
+        senc = settings._encode_steps(state)
+        sheld = getattr(self, "_set_step_key", b"")
+        if senc[0] != sheld and sheld:
+            check(lib.dsl_set_step_invariants(self.handle, None, 0, None, 0), "dsl_set_step_invariants")
+            self._set_step_key = sheld = b""
         if enc is not getattr(self, "_set_enc", None):  # the engine keeps the settings it was given
             check(lib.dsl_set_settings(self.handle, ctypes.byref(enc)), "dsl_set_settings")
             self._set_enc = enc
@@ -1019,6 +1214,9 @@ class Engine:
         if settings._watches and settings._witness_mask() != getattr(self, "_set_witness_mask", 0):
             check(lib.dsl_set_watch_witnesses(self.handle, settings._witness_mask()), "dsl_set_watch_witnesses")
             self._set_witness_mask = settings._witness_mask()
+        if senc[0] != sheld:
+            check(lib.dsl_set_step_invariants(self.handle, senc[1], senc[2], senc[3], senc[4]), "dsl_set_step_invariants")
+            self._set_step_key = senc[0]
         # the event census: told only when it differs from what the engine holds
         if settings._event_census != getattr(self, "_set_event_census", False):
             check(lib.dsl_set_event_census(self.handle, int(settings._event_census)), "dsl_set_event_census")
@@ -1059,6 +1257,16 @@ class Engine:
                                         for c in range(ncls)])
             res._event_classes = self.protocol.event_classes()
             res._event_addresses = list(self.protocol.addresses)
+        if settings._step_invariants:  # the step invariants' edge rows and violation of this run
+            n, total = ctypes.c_int32(0), ctypes.c_uint64(0)
+            buf = (ctypes.c_uint64 * max(1, len(res.per_depth)))()
+            check(self.lib.dsl_step_edges(self.handle, buf, len(res.per_depth), ctypes.byref(n), ctypes.byref(total)),
+                  "dsl_step_edges")
+            res._step_edges = [buf[i] for i in range(min(n.value, len(res.per_depth)))]
+            res._step_violation = self._step_violation_of(state, settings, len(res.per_depth) + 1)
+            sv = res._step_violation
+            if sv is not None and res._end == EndCondition.INVARIANT_VIOLATED and res._predicate is None:
+                res._predicate = PredicateResult(_step_invariant(settings, sv.index), False)  # the reported terminal
         if any(settings._witness):  # the witnesses of this run (dsl_watch_witness)
             base = state.trace() if state.packed is not None else []
             nb = self.state_bytes()
@@ -1066,6 +1274,24 @@ class Engine:
                 res._witnesses.append(self._witness_state(w, len(res.per_depth), nb, base, state._dropped) if want
                                       else None)
         return res
+
+    def _step_violation_of(self, state: SearchState, settings: SearchSettings, cap: int) -> Optional[StepViolation]:
+        nb = self.state_bytes()
+        idx, depth, n, edges = ctypes.c_int32(-1), ctypes.c_int32(-1), ctypes.c_int32(0), ctypes.c_uint64(0)
+        per = (ctypes.c_uint64 * _lib.DSL_MAX_STEP_INVARIANTS)()
+        tr = (_lib.dsl_event * max(1, cap))()
+        pbuf, xbuf = (ctypes.c_uint8 * nb)(), (ctypes.c_uint8 * nb)()
+        check(self.lib.dsl_step_violation(self.handle, ctypes.byref(idx), ctypes.byref(depth), ctypes.byref(edges), per,
+                                          tr, cap, ctypes.byref(n), pbuf, xbuf, nb), "dsl_step_violation")
+        if idx.value < 0:
+            return None
+        raw = [_lib.dsl_event.from_buffer_copy(tr[i]) for i in range(min(n.value, cap))]
+        base = state.trace() if state.packed is not None else []
+        ev = [self.protocol.render_event(e) for e in raw]
+        parent = SearchState(self.protocol, bytes(pbuf), depth.value - 1, base + ev[:-1], raw[:-1], state._dropped)
+        succ = SearchState(self.protocol, bytes(xbuf), depth.value, base + ev, raw, state._dropped)
+        return StepViolation(idx.value, settings._step_invariants[idx.value].name, depth.value, parent, succ, ev[-1],
+                             edges.value, [per[i] for i in range(len(settings._step_invariants))])
 
     def _witness_state(self, w: int, cap: int, nb: int, base: List[str], dropped) -> Optional[SearchState]:
         depth, n = ctypes.c_int32(-1), ctypes.c_int32(0)
@@ -1150,7 +1376,9 @@ class Engine:
                 if r.terminal_depth >= 0:
                     terminal = last
                 if end == EndCondition.INVARIANT_VIOLATED:
-                    pred = PredicateResult(settings.invariants()[r.predicate_index], False)
+                    ninv = len(settings._invariants)  # past them: a step invariant (Engine.bfs names it)
+                    pred = PredicateResult(settings.invariants()[r.predicate_index], False) \
+                        if r.predicate_index < ninv else None
                 elif end == EndCondition.GOAL_FOUND:
                     pred = PredicateResult(settings.goals()[r.predicate_index], True)
             res = SearchResults(end, r.states, per_depth, r.initial_depth, r.max_depth, terminal, pred,
@@ -1168,7 +1396,9 @@ class Engine:
                     [_lib.dsl_event.from_buffer_copy(e) for e in t_raw], state._dropped)
                 t_pred = None
                 if t_end == EndCondition.INVARIANT_VIOLATED:
-                    t_pred = PredicateResult(settings.invariants()[t.predicate_index], False)
+                    t_pred = PredicateResult(_step_invariant(settings, t.predicate_index - len(settings._invariants)), False) \
+                        if t.predicate_index >= len(settings._invariants) else \
+                        PredicateResult(settings.invariants()[t.predicate_index], False)
                 elif t_end == EndCondition.GOAL_FOUND:
                     t_pred = PredicateResult(settings.goals()[t.predicate_index], True)
                 res._terminals.append((t_end, t_pred, t_state))
@@ -1182,6 +1412,11 @@ class Engine:
             return res
         finally:
             lib.dsl_result_free(res_p)
+
+
+def _step_invariant(settings: SearchSettings, index: int) -> StatePredicate:
+    """Step invariant ``index`` of the settings."""
+    return settings._step_invariants[index]
 
 
 class Search:

@@ -49,7 +49,9 @@ extern "C" {
                             Still 6 with dsl_set_watch_witnesses / dsl_watch_witness: the same again
                             Still 6 with dsl_set_event_census / dsl_event_census / dsl_event_class_count /
                             _name / _is_timer: five entry points and dsl_event_count are added;
-                            dsl_settings, dsl_result and dsl_stats keep their bytes */
+                            dsl_settings, dsl_result and dsl_stats keep their bytes
+                            Still 6 with dsl_set_step_invariants / dsl_step_edges / dsl_step_violation and
+                            the DSL_PRED_STEP_* leaves: three entry points, no struct changes */
 #define DSL_MAX_NODES 32
 #define DSL_MAX_PREDICATES 16
 #define DSL_MAX_POOL 48          /* operands of combinator predicates (dsl_settings.pool) */
@@ -154,8 +156,33 @@ typedef enum {
   /* One condition of a DSL_PRED_NET: an unsigned comparison of a bit field of the record with a
    * constant. Legal only as a pool entry that a DSL_PRED_NET refers to (never a predicate, never a
    * combinator's operand); negate must be 0. Encoding below (DSL_REC_*). */
-  DSL_PRED_REC_COND = 952
+  DSL_PRED_REC_COND = 952,
+  /* The step leaves: legal only inside a step invariant (dsl_set_step_invariants below), where a
+   * predicate is judged on an edge (parent P, event E, successor X). Anywhere else -- invariants,
+   * goals, prunes, watches -- they are refused with DSL_ERR_ARG.
+   * DSL_PRED_STEP_FIELD: DSL_PRED_FIELD's encoding plus two bits of arg0: bit 36 = the left operand
+   * is read from X (otherwise from P), bit 37 = the same for a right operand that is a field.
+   * Unsigned comparison, never throws, any two nodes; descriptors are checked as DSL_PRED_FIELD's. */
+  DSL_PRED_STEP_FIELD = 953,
+  /* DSL_PRED_STEP_SENT: the step added to the network a record satisfying all of the leaf's
+   * conditions; DSL_PRED_NET's pool encoding (arg0 = first DSL_PRED_REC_COND entry, arg1 = their
+   * number), counted against DSL_MAX_NET_CONDS_TOTAL. "Added" means new to P's record set: the
+   * network is a set, so a record the handler sends again while P already holds it is NOT added
+   * and does not match. */
+  DSL_PRED_STEP_SENT = 954,
+  /* DSL_PRED_STEP_EVENT: E is of handler class arg0 (an index of dsl_event_class_name's range, -1 =
+   * any) and is delivered to node arg1 (-1 = any; a timer's node is its own). An event the engine
+   * would skip as a proven no-op is judged under its real class, as the event census counts it. */
+  DSL_PRED_STEP_EVENT = 955
 } dsl_predicate_id;
+
+#define DSL_STEP_LHS_NEW_BIT 36
+#define DSL_STEP_RHS_NEW_BIT 37
+#define DSL_STEP_FIELD_ARG0(desc, cmp, rhs_is_field, lhs_new, rhs_new)                    \
+  (DSL_FIELD_ARG0(desc, cmp, rhs_is_field) | ((int64_t)((lhs_new) ? 1 : 0) << DSL_STEP_LHS_NEW_BIT) | \
+   ((int64_t)((rhs_new) ? 1 : 0) << DSL_STEP_RHS_NEW_BIT))
+#define DSL_STEP_ARG0_LHS_NEW(arg0) ((int)(((uint64_t)(arg0) >> DSL_STEP_LHS_NEW_BIT) & 1u))
+#define DSL_STEP_ARG0_RHS_NEW(arg0) ((int)(((uint64_t)(arg0) >> DSL_STEP_RHS_NEW_BIT) & 1u))
 
 /* DSL_PRED_FIELD. A field descriptor (27 bits) names `width` bits (1..32) from bit `bit` of node
  * `node`'s words (bit 0 = the least significant bit of the node's word 0; the field lies inside
@@ -464,6 +491,54 @@ int dsl_set_event_census(dsl_engine* e, int32_t on);
    the census). A null engine, or a level outside [0, n_levels) with non-null cells, is DSL_ERR_ARG
    (named in dsl_last_error). */
 int dsl_event_census(dsl_engine* e, int32_t level, dsl_event_count* cells, int32_t* n_levels);
+
+/* Step invariants: predicates over an edge (P, E, X) -- P a state the BFS expands, E one of its
+ * enabled events, X the successor -- where an invariant is a predicate over one state. Opt-in, for
+ * dsl_run on one shard.
+ * Judged edges: every edge whose handler returns normally and whose successor differs from its
+ * parent (the event census's events - noops - exceptions). A stuttering step (X == P) is exempt, an
+ * exceptional step has no successor and is not judged; an edge is judged whether X is new, already
+ * visited, pruned, a goal or a maxDepth state. The unexpanded maxDepth frontier has no outgoing
+ * edges; the start state has no incoming one.
+ * A step invariant whose value is false, or that threw, is violated. The search ends at the first
+ * level with a violated edge, and that level is completed as always. Priority within the level:
+ * EXCEPTION > state INVARIANT > step INVARIANT > GOAL. When the level's best terminal is an
+ * exception or a state invariant it is reported exactly as without step invariants (and
+ * dsl_step_violation still answers). Otherwise end_condition = DSL_INVARIANT_VIOLATED,
+ * terminal_depth = depth(P) + 1 (also when X was first discovered shallower), predicate_index =
+ * n_invariants + s for the lowest violated step invariant s of the reported edge, the trace is a
+ * shortest trace of P followed by E, terminal_state is X, and with max_terminals > 0 the list is
+ * that terminal alone (terminals_total = 1).
+ * The reported edge is, among the level's violating edges, the one with the smallest (P's
+ * fingerprint hi, lo, event index): it depends on no arrival order, chunking, table size or restart.
+ * Step invariants that hold change nothing: the same states, per_depth, end condition, terminals,
+ * traces, watch counts, witnesses and census (the levels run one by one, as with the census). A
+ * restarted search counts from zero. The pass has no deadline check of its own: a violation found
+ * in a level that max_time_ms then cuts short is reported, and that level has no edge row.
+ * Inside a step invariant: the three step leaves, DSL_PRED_FIELD and the protocol's named leaves
+ * (both evaluated on X), negate and the combinators; DSL_PRED_NET is refused (DSL_ERR_ARG).
+ * dsl_run with step invariants and virtual_shards > 1 or world_size > 1 returns DSL_ERR_ARG before
+ * any collective. dsl_run_dfs, dsl_replay and dsl_human_readable_trace ignore them. */
+#define DSL_MAX_STEP_INVARIANTS 8
+/* Replaces the engine's step invariants (n = 0 clears them); `pool` as for dsl_set_watches. Kept
+   across dsl_set_settings. They share the 64 program steps, the 16-deep stack and the
+   DSL_MAX_NET_CONDS_TOTAL conditions with the settings and the watches; whichever call makes a sum
+   overflow is refused (DSL_ERR_ARG) and the engine keeps what it had. */
+int dsl_set_step_invariants(dsl_engine* e, const dsl_predicate* preds, int32_t n, const dsl_predicate* pool,
+                            int32_t n_pool);
+/* Edges judged per completed level of the last dsl_run: per_level[i] (up to cap written, *n_levels =
+   the rows there are, one per level as the census's rows) for the parents of depth initial_depth + i;
+   *total their sum. No rows after any other call or without step invariants. */
+int dsl_step_edges(dsl_engine* e, uint64_t* per_level, int32_t cap, int32_t* n_levels, uint64_t* total);
+/* The step violation of the last dsl_run: *index = the lowest violated step invariant of the
+   reported edge, or -1 when there is none or the last call was not a dsl_run; *depth = depth(P) + 1;
+   *edges_violating = the level's violating edges; per_invariant[s] = those violating step invariant
+   s (an edge counts for every one it violates); up to cap events of the trace (which ends with E)
+   written to `trace`, *trace_len = its full length; parent_state / state = P / X, filled when len is
+   the packed state's size. Any out pointer may be NULL. */
+int dsl_step_violation(dsl_engine* e, int32_t* index, int32_t* depth, uint64_t* edges_violating,
+                       uint64_t per_invariant[DSL_MAX_STEP_INVARIANTS], dsl_event* trace, int32_t cap,
+                       int32_t* trace_len, uint8_t* parent_state, uint8_t* state, size_t len);
 
 /* Random depth-first search (Search.dfs / RandomDFS, Search.java:397-402, :507-583): `probes`
  * independent random walks run concurrently on the device (one per lane), each restarted from

@@ -13,6 +13,9 @@
 // each; a result is 7 PutOk, 6 KeyNotFound or a value. The application state is a function of the
 // executed log prefix, so it is recomputed, not stored. Server Tick timers (100 ms) are re-set on
 // every fire; a client's ClientTimer(seq) (100 ms) re-sends while its command is pending.
+// The last parameter, mutant (0 = the protocol), breaks it on purpose so that a search finds a log
+// invariant false: 1 (adopt-chosen-only) makes phase 1 merge only CHOSEN entries, 2 (accept-stale)
+// makes an acceptor accept a P2a of a ballot below its own.
 #pragma once
 #include "../../nodestate.hpp"
 
@@ -32,9 +35,11 @@ struct MultiPaxosIR {
     int32_t op[2][3];
     int32_t val[2][3];
     int32_t expected[2][3];
+    int32_t mutant[1][1];
     uint64_t ncmd_pk;  // ncmd[r][c] at bit 2 * (r * 1 + c) (from_desc)
     uint64_t op_pk;  // op[r][c] at bit 2 * (r * 3 + c) (from_desc)
     uint64_t val_pk;  // val[r][c] at bit 2 * (r * 3 + c) (from_desc)
+    uint64_t mutant_pk;  // mutant[r][c] at bit 2 * (r * 1 + c) (from_desc)
   };
   static DSL_HD int get(const uint32_t* w, int bit, int width) { return field_get<kNodeWords>(w, bit, width); }
   static DSL_HD void put(uint32_t* w, int bit, int width, int v) { field_put<kNodeWords>(w, bit, width, v); }
@@ -437,7 +442,7 @@ struct MultiPaxosIR {
     if (((l_me222 & 3) == 2)) {
       arr_put_server_p1blog(w, 0, ((2 | (0 << 2)) | (((l_me222 >> 8) & 7) << 8)));
     } else {
-      if (((((l_me222 & 3) == 1) && ((l_mm223 & 3) != 2)) && (((l_mm223 & 3) == 0) || (((l_mm223 >> 2) & 63) < ((l_me222 >> 2) & 63))))) {
+      if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me222 & 3) == 1)) && ((l_mm223 & 3) != 2)) && (((l_mm223 & 3) == 0) || (((l_mm223 >> 2) & 63) < ((l_me222 >> 2) & 63))))) {
         arr_put_server_p1blog(w, 0, l_me222);
       }
     }
@@ -446,7 +451,7 @@ struct MultiPaxosIR {
     if (((l_me224 & 3) == 2)) {
       arr_put_server_p1blog(w, 1, ((2 | (0 << 2)) | (((l_me224 >> 8) & 7) << 8)));
     } else {
-      if (((((l_me224 & 3) == 1) && ((l_mm225 & 3) != 2)) && (((l_mm225 & 3) == 0) || (((l_mm225 >> 2) & 63) < ((l_me224 >> 2) & 63))))) {
+      if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me224 & 3) == 1)) && ((l_mm225 & 3) != 2)) && (((l_mm225 & 3) == 0) || (((l_mm225 >> 2) & 63) < ((l_me224 >> 2) & 63))))) {
         arr_put_server_p1blog(w, 1, l_me224);
       }
     }
@@ -455,7 +460,7 @@ struct MultiPaxosIR {
     if (((l_me226 & 3) == 2)) {
       arr_put_server_p1blog(w, 2, ((2 | (0 << 2)) | (((l_me226 >> 8) & 7) << 8)));
     } else {
-      if (((((l_me226 & 3) == 1) && ((l_mm227 & 3) != 2)) && (((l_mm227 & 3) == 0) || (((l_mm227 >> 2) & 63) < ((l_me226 >> 2) & 63))))) {
+      if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me226 & 3) == 1)) && ((l_mm227 & 3) != 2)) && (((l_mm227 & 3) == 0) || (((l_mm227 >> 2) & 63) < ((l_me226 >> 2) & 63))))) {
         arr_put_server_p1blog(w, 2, l_me226);
       }
     }
@@ -464,7 +469,7 @@ struct MultiPaxosIR {
     if (((l_me228 & 3) == 2)) {
       arr_put_server_p1blog(w, 3, ((2 | (0 << 2)) | (((l_me228 >> 8) & 7) << 8)));
     } else {
-      if (((((l_me228 & 3) == 1) && ((l_mm229 & 3) != 2)) && (((l_mm229 & 3) == 0) || (((l_mm229 >> 2) & 63) < ((l_me228 >> 2) & 63))))) {
+      if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me228 & 3) == 1)) && ((l_mm229 & 3) != 2)) && (((l_mm229 & 3) == 0) || (((l_mm229 >> 2) & 63) < ((l_me228 >> 2) & 63))))) {
         arr_put_server_p1blog(w, 3, l_me228);
       }
     }
@@ -478,7 +483,7 @@ struct MultiPaxosIR {
   static DSL_HD int hm_server_P2a(int i, uint32_t* w, Rec r, O& out, const Params& p, int& fl) {
     (void)i; (void)w; (void)r; (void)out; (void)p; (void)fl;
     const int l_b = (((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u));
-    if ((l_b < ((get(w, 0, 4) << 2) | get(w, 4, 2)))) {
+    if (((l_b < ((get(w, 0, 4) << 2) | get(w, 4, 2))) && ((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 2))) {
       return STEP_OK;
     }
     if ((l_b > ((get(w, 0, 4) << 2) | get(w, 4, 2)))) {
@@ -610,7 +615,7 @@ struct MultiPaxosIR {
           if (((l_me231 & 3) == 2)) {
             arr_put_server_p1blog(w, 0, ((2 | (0 << 2)) | (((l_me231 >> 8) & 7) << 8)));
           } else {
-            if (((((l_me231 & 3) == 1) && ((l_mm232 & 3) != 2)) && (((l_mm232 & 3) == 0) || (((l_mm232 >> 2) & 63) < ((l_me231 >> 2) & 63))))) {
+            if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me231 & 3) == 1)) && ((l_mm232 & 3) != 2)) && (((l_mm232 & 3) == 0) || (((l_mm232 >> 2) & 63) < ((l_me231 >> 2) & 63))))) {
               arr_put_server_p1blog(w, 0, l_me231);
             }
           }
@@ -619,7 +624,7 @@ struct MultiPaxosIR {
           if (((l_me233 & 3) == 2)) {
             arr_put_server_p1blog(w, 1, ((2 | (0 << 2)) | (((l_me233 >> 8) & 7) << 8)));
           } else {
-            if (((((l_me233 & 3) == 1) && ((l_mm234 & 3) != 2)) && (((l_mm234 & 3) == 0) || (((l_mm234 >> 2) & 63) < ((l_me233 >> 2) & 63))))) {
+            if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me233 & 3) == 1)) && ((l_mm234 & 3) != 2)) && (((l_mm234 & 3) == 0) || (((l_mm234 >> 2) & 63) < ((l_me233 >> 2) & 63))))) {
               arr_put_server_p1blog(w, 1, l_me233);
             }
           }
@@ -628,7 +633,7 @@ struct MultiPaxosIR {
           if (((l_me235 & 3) == 2)) {
             arr_put_server_p1blog(w, 2, ((2 | (0 << 2)) | (((l_me235 >> 8) & 7) << 8)));
           } else {
-            if (((((l_me235 & 3) == 1) && ((l_mm236 & 3) != 2)) && (((l_mm236 & 3) == 0) || (((l_mm236 >> 2) & 63) < ((l_me235 >> 2) & 63))))) {
+            if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me235 & 3) == 1)) && ((l_mm236 & 3) != 2)) && (((l_mm236 & 3) == 0) || (((l_mm236 >> 2) & 63) < ((l_me235 >> 2) & 63))))) {
               arr_put_server_p1blog(w, 2, l_me235);
             }
           }
@@ -637,7 +642,7 @@ struct MultiPaxosIR {
           if (((l_me237 & 3) == 2)) {
             arr_put_server_p1blog(w, 3, ((2 | (0 << 2)) | (((l_me237 >> 8) & 7) << 8)));
           } else {
-            if (((((l_me237 & 3) == 1) && ((l_mm238 & 3) != 2)) && (((l_mm238 & 3) == 0) || (((l_mm238 >> 2) & 63) < ((l_me237 >> 2) & 63))))) {
+            if ((((((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 1) && ((l_me237 & 3) == 1)) && ((l_mm238 & 3) != 2)) && (((l_mm238 & 3) == 0) || (((l_mm238 >> 2) & 63) < ((l_me237 >> 2) & 63))))) {
               arr_put_server_p1blog(w, 3, l_me237);
             }
           }
@@ -1953,7 +1958,7 @@ struct MultiPaxosIR {
     x = (is_server(i, p) && rec_type(r) == 0) ? (bool)((get(w, 6, 1) == 0)) : x;  // server <- Request
     x = (is_server(i, p) && rec_type(r) == 2) ? (bool)(((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) < ((get(w, 0, 4) << 2) | get(w, 4, 2)))) : x;  // server <- P1a
     x = (is_server(i, p) && rec_type(r) == 3) ? (bool)(((get(w, 7, 1) == 0) || ((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) != ((get(w, 0, 4) << 2) | get(w, 4, 2))))) : x;  // server <- P1b
-    x = (is_server(i, p) && rec_type(r) == 4) ? (bool)(((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) < ((get(w, 0, 4) << 2) | get(w, 4, 2)))) : x;  // server <- P2a
+    x = (is_server(i, p) && rec_type(r) == 4) ? (bool)((((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) < ((get(w, 0, 4) << 2) | get(w, 4, 2))) && ((int)((p.mutant_pk >> ((2 * ((0) * 1 + (0))) & 63)) & 3u) != 2))) : x;  // server <- P2a
     x = (is_server(i, p) && rec_type(r) == 5) ? (bool)(((((get(w, 6, 1) == 0) || ((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) != ((get(w, 0, 4) << 2) | get(w, 4, 2)))) || ((arr_server_log(w, ((int)((r >> 6) & 7u) - 1)) & 3) != 1)) || ((((arr_server_votes(w, ((int)((r >> 6) & 7u) - 1)) >> (rec_from(r) - (first_server(p) + 1 - 1))) & 1) != 0) && (!(((((arr_server_votes(w, ((int)((r >> 6) & 7u) - 1)) & 1) + ((arr_server_votes(w, ((int)((r >> 6) & 7u) - 1)) >> 1) & 1)) + ((arr_server_votes(w, ((int)((r >> 6) & 7u) - 1)) >> 2) & 1)) * 2) > p.servers))))) : x;  // server <- P2b
     x = (is_server(i, p) && rec_type(r) == 6) ? (bool)(((arr_server_log(w, ((int)((r >> 0) & 7u) - 1)) & 3) == 2)) : x;  // server <- Decision
     x = (is_server(i, p) && rec_type(r) == 7) ? (bool)((((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) < ((get(w, 0, 4) << 2) | get(w, 4, 2))) || (((((int)((r >> 0) & 15u) << 2) | (int)((r >> 4) & 3u)) == ((get(w, 0, 4) << 2) | get(w, 4, 2))) && (get(w, 8, 1) != 0)))) : x;  // server <- Heartbeat
@@ -1973,6 +1978,9 @@ struct MultiPaxosIR {
     for (int r = 0; r < 2; r++)
       for (int c = 0; c < 3; c++)
         if (p.expected[r][c] < -1 || p.expected[r][c] > 4095) return false;
+    for (int r = 0; r < 1; r++)
+      for (int c = 0; c < 1; c++)
+        if (p.mutant[r][c] < 0 || p.mutant[r][c] > 2) return false;
     return p.servers >= 1 && p.servers <= 3 &&
            p.clients >= 1 && p.clients <= 2 &&
            p.servers >= 1 && p.servers <= 3 &&
@@ -2002,6 +2010,11 @@ struct MultiPaxosIR {
         const int q = 16 + r * 3 + c;
         p.expected[r][c] = d.n_params > q ? (int32_t)d.params[q] : -1;
       }
+    for (int r = 0; r < 1; r++)
+      for (int c = 0; c < 1; c++) {
+        const int q = 22 + r * 1 + c;
+        p.mutant[r][c] = d.n_params > q ? (int32_t)d.params[q] : 0;
+      }
     for (int r = 0; r < 2; r++)
       for (int c = 0; c < 1; c++)
         p.ncmd_pk |= (uint64_t)((uint32_t)p.ncmd[r][c] & 3u) << (2 * (r * 1 + c));
@@ -2011,6 +2024,9 @@ struct MultiPaxosIR {
     for (int r = 0; r < 2; r++)
       for (int c = 0; c < 3; c++)
         p.val_pk |= (uint64_t)((uint32_t)p.val[r][c] & 3u) << (2 * (r * 3 + c));
+    for (int r = 0; r < 1; r++)
+      for (int c = 0; c < 1; c++)
+        p.mutant_pk |= (uint64_t)((uint32_t)p.mutant[r][c] & 3u) << (2 * (r * 1 + c));
     return p;
   }
   static void describe_message(Rec r, dsl_event* e) {

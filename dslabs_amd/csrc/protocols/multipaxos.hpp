@@ -62,13 +62,16 @@ struct MultiPaxos {
     // select chain over the arrays above): cmdtab bits 4*cmd .. +3 = op << 2 | value token of
     // command id cmd (1..6); exptab[c] bits 16*k .. +15 = 0x8000 | expected[c][k] (0 = no check).
     uint32_t cmdtab;
-    uint32_t pad;
+    uint32_t mutant;  // 0 = the protocol; MUT_ADOPT_CHOSEN_ONLY, MUT_ACCEPT_STALE
     uint64_t exptab[kMaxClients];
   };
   enum { OP_PUT = 1, OP_APPEND = 2, OP_GET = 3 };
   static constexpr uint32_t kPutOk = 7, kKeyNotFound = 6;  // result codes beside values (len 1..4)
   enum { M_REQUEST = 0, M_REPLY, M_P1A, M_P1B, M_P2A, M_P2B, M_DECISION, M_HEARTBEAT, T_TICK = 8, T_CLIENT = 9 };
   enum { EMPTY = 0, ACCEPTED = 1, CHOSEN = 2 };
+  // Mutants, for searches that must find a log invariant false: phase 1 merges only CHOSEN entries
+  // (its own log's and the P1b logs'); an acceptor accepts a P2a of a ballot below its own.
+  enum { MUT_ADOPT_CHOSEN_ONLY = 1, MUT_ACCEPT_STALE = 2 };
 
   // Handler class of a message (< kMsgClasses; timers are class kMsgClasses): k_level groups a chunk's work items
   // by class so that the lanes of a wavefront run the same handler.
@@ -251,11 +254,12 @@ struct MultiPaxos {
     bcast_servers(s, p, M_P2A, ballot_field(b) | ((uint64_t)slot << 6) | ((uint64_t)cmd << 9), out);
     if (majority(p, 1 << s)) choose(s, w, p, slot, out);  // a one-server group
   }
-  static DSL_HD void merge(uint32_t* w, int slot, uint32_t e) {
+  static DSL_HD void merge(uint32_t* w, const Params& p, int slot, uint32_t e) {
     const uint32_t m = p1entry(w, slot);
     if (e_status(e) == CHOSEN) {
       set_p1entry(w, slot, mk_entry(CHOSEN, 0, e_cmd(e)));
-    } else if (e_status(e) == ACCEPTED && e_status(m) != CHOSEN && (e_status(m) == EMPTY || e_ballot(m) < e_ballot(e))) {
+    } else if (p.mutant != MUT_ADOPT_CHOSEN_ONLY && e_status(e) == ACCEPTED && e_status(m) != CHOSEN &&
+               (e_status(m) == EMPTY || e_ballot(m) < e_ballot(e))) {  // adopt-chosen-only drops accepted entries
       set_p1entry(w, slot, e);
     }
   }
@@ -376,7 +380,7 @@ struct MultiPaxos {
         w[4] = 0;
         w[5] = 0;
 #pragma unroll
-        for (int k = 1; k <= kSlots; k++) merge(w, k, entry(w, k));
+        for (int k = 1; k <= kSlots; k++) merge(w, p, k, entry(w, k));
         bcast_servers(s, p, M_P1A, ballot_field(cmp_ballot(w)), out);
         if (majority(p, 1 << s)) {  // a one-server group leads at once
           become_leader(s, w, p, out);
@@ -417,7 +421,8 @@ struct MultiPaxos {
     const bool p2b = !act || b != cur || e_status(e) != ACCEPTED || (((v >> from) & 1) && !majority(p, v));
     bool server = false;
     server = type == M_REQUEST ? !act : server;
-    server = (type == M_P2A || type == M_P1A) ? b < cur : server;
+    server = type == M_P1A ? b < cur : server;
+    server = type == M_P2A ? (b < cur && p.mutant != MUT_ACCEPT_STALE) : server;
     server = type == M_HEARTBEAT ? (b < cur || (b == cur && hrd)) : server;
     server = type == M_P2B ? p2b : server;
     server = type == M_DECISION ? e_status(e) == CHOSEN : server;
@@ -466,8 +471,8 @@ struct MultiPaxos {
     } else {
       const int b = m_ballot(m);
       switch (type) {
-        case M_P2A: {
-          if (b < cmp_ballot(w)) return STEP_OK;
+        case M_P2A: {  // accept-stale goes on with a lower ballot: adopt() leaves the ballot
+          if (b < cmp_ballot(w) && p.mutant != MUT_ACCEPT_STALE) return STEP_OK;
           adopt(w, b);
           put(w, 8, 1, 1);
           const int slot = (int)((m >> 6) & 7), cmd = (int)((m >> 9) & 7);
@@ -514,7 +519,7 @@ struct MultiPaxos {
           const int v = p1votes(w) | (1 << from);
           put(w, 11, 3, v);
 #pragma unroll
-          for (int k = 1; k <= kSlots; k++) merge(w, k, (uint32_t)((m >> (6 + 11 * (k - 1))) & 0x7ff));
+          for (int k = 1; k <= kSlots; k++) merge(w, p, k, (uint32_t)((m >> (6 + 11 * (k - 1))) & 0x7ff));
           if (!majority(p, v)) return STEP_OK;
           lead = true;
           break;
@@ -730,6 +735,7 @@ struct MultiPaxos {
   }
   static bool valid(const Params& p) {
     if (p.servers < 1 || p.servers > kMaxServers || p.clients < 1 || p.clients > kMaxClients) return false;
+    if (p.mutant > MUT_ACCEPT_STALE) return false;
     int tokens = 0;  // the key's value never exceeds kMaxTokens (every Put / Append adds at most one)
     for (int c = 0; c < p.clients; c++) {
       if (p.ncmds[c] < 1 || p.ncmds[c] > kMaxCmds) return false;
@@ -742,7 +748,8 @@ struct MultiPaxos {
     }
     return tokens <= kMaxTokens;
   }
-  // params: servers, clients, then per client: ncmds, ops[3], vals[3], expected[3]
+  // params: servers, clients, then per client: ncmds, ops[3], vals[3], expected[3]; then mutant
+  // (absent = 0, the protocol)
   static Params from_desc(const dsl_protocol_desc& d) {
     Params p{};
     p.servers = (int32_t)d.params[0];
@@ -756,6 +763,8 @@ struct MultiPaxos {
         p.expected[c][k] = (int32_t)d.params[b + 1 + 2 * kMaxCmds + k];
       }
     }
+    const int mi = 2 + (1 + 3 * kMaxCmds) * kMaxClients;
+    p.mutant = d.n_params > mi ? (uint32_t)d.params[mi] : 0u;
     for (int c = 0; c < kMaxClients; c++)
       for (int k = 0; k < kMaxCmds; k++) {
         const int cmd = cmd_id(c, k + 1);

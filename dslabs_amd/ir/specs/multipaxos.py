@@ -11,7 +11,10 @@ Command id 1 + 3 c + (q - 1) is client c's q-th command (0 = no-op); its KV op (
 3 Get) and value token come from the workload tables. The key's value is len:3 | tokens 2 bits
 each; a result is 7 PutOk, 6 KeyNotFound or a value. The application state is a function of the
 executed log prefix, so it is recomputed, not stored. Server Tick timers (100 ms) are re-set on
-every fire; a client's ClientTimer(seq) (100 ms) re-sends while its command is pending."""
+every fire; a client's ClientTimer(seq) (100 ms) re-sends while its command is pending.
+The last parameter, mutant (0 = the protocol), breaks it on purpose so that a search finds a log
+invariant false: 1 (adopt-chosen-only) makes phase 1 merge only CHOSEN entries, 2 (accept-stale)
+makes an acceptor accept a P2a of a ballot below its own."""
 import itertools
 
 from ... import _lib
@@ -24,6 +27,7 @@ P.param_table("ncmd", 2, 1, 0, 3)
 P.param_table("op", 2, 3, 0, 3)       # 1 Put, 2 Append, 3 Get
 P.param_table("val", 2, 3, 0, 3)      # value token 1..3 (0 for a Get)
 P.param_table("expected", 2, 3, -1, 4095, default=-1)
+P.param_table("mutant", 1, 1, 0, 2)   # one entry, a table so that it follows the existing parameters
 P.workload_size = lambda h, c: h.ptab("ncmd", c, 0)
 P.expected_result = lambda c, k: Expr(f"sel_param(p.expected, {c.dev}, {k.dev} - 1)",
                                       f"prm.expected[{c.orc}][{k.orc} - 1]")
@@ -33,6 +37,7 @@ P.sends_distinct = True  # distinct destinations or slots per send (protocheck: 
 EMPTY, ACCEPTED, CHOSEN = 0, 1, 2
 PUT, APPEND, GET = 1, 2, 3
 PUT_OK, KEY_NOT_FOUND = 7, 6
+ADOPT_CHOSEN_ONLY, ACCEPT_STALE = 1, 2
 SLOTS, MAX_ROUND = 4, 15
 
 # message types in the hand-written protocol's order (its handler classes)
@@ -105,6 +110,10 @@ def cmd_seq(cmd):
 
 def me(h):
     return h.index(server)
+
+
+def mutant(h):
+    return h.ptab("mutant", 0, 0)
 
 
 # ---- helpers (inlined statements) -----------------------------------------------------------------
@@ -194,7 +203,8 @@ def merge(h, slot, e):
     with h.if_(st(e) == CHOSEN):
         h.set_at("p1blog", slot - 1, mk(CHOSEN, 0, ec(e)))
     with h.else_():
-        with h.if_((st(e) == ACCEPTED) & (st(m) != CHOSEN) & ((st(m) == EMPTY) | (eb(m) < eb(e)))):
+        with h.if_((mutant(h) != ADOPT_CHOSEN_ONLY) & (st(e) == ACCEPTED) & (st(m) != CHOSEN) &
+                   ((st(m) == EMPTY) | (eb(m) < eb(e)))):
             h.set_at("p1blog", slot - 1, e)
 
 
@@ -279,7 +289,7 @@ def _request(h):
 @server.on(P2a)
 def _p2a(h):
     b = h.let("b", mballot(h))
-    with h.if_(b < ballot(h)):
+    with h.if_((b < ballot(h)) & (mutant(h) != ACCEPT_STALE)):  # accept-stale goes on: adopt leaves the ballot
         h.ret()
     adopt(h, b)
     h.set("heard", 1)
@@ -392,7 +402,7 @@ def _n_request(h):
 
 @server.noop(P2a)
 def _n_p2a(h):
-    return mballot(h) < ballot(h)
+    return (mballot(h) < ballot(h)) & (mutant(h) != ACCEPT_STALE)
 
 
 @server.noop(P1a)

@@ -183,7 +183,12 @@ class MultiPaxos(Protocol):
     """lab3 Multi-Paxos (builder-authored): servers "server1..n", clients
     "client1..c"; each client runs a KVStoreWorkload of Put / Append / Get commands on the key
     "foo" (KVStoreWorkload.java:40-66, :184-188). Values are token sequences (a workload's
-    tokens, <= 4 per value); result codes: 7 PutOk, 6 KeyNotFound, else a value."""
+    tokens, <= 4 per value); result codes: 7 PutOk, 6 KeyNotFound, else a value.
+
+    ``mutant`` (a MUTANTS name or its number; 0 = the protocol) breaks it on purpose, so that a
+    search finds a log invariant false: "adopt-chosen-only" makes phase 1 merge only CHOSEN entries
+    (a new leader re-proposes over accepted ones); "accept-stale" makes an acceptor accept a P2a of
+    a ballot below its own."""
 
     proto_id = DSL_PROTO_MULTIPAXOS
     node_words = 6
@@ -193,6 +198,7 @@ class MultiPaxos(Protocol):
     OPS = {"PUT": 1, "APPEND": 2, "GET": 3}
     PUT_OK, KEY_NOT_FOUND = 7, 6
     STATUS = {"EMPTY": 0, "ACCEPTED": 1, "CHOSEN": 2, "CLEARED": 3}  # PaxosLogSlotStatus
+    MUTANTS = {"none": 0, "adopt-chosen-only": 1, "accept-stale": 2}  # the oracle's --mutant names
     WORKLOADS = {  # same names as the oracle's --workload: (commands, expected results, value tokens)
         "append-xy": ([["APPEND:foo:X"], ["APPEND:foo:Y"]], [[], []], ["X", "Y", "Z"]),
         "append-xy-expect": ([["APPEND:foo:X"], ["APPEND:foo:Y"]], [["X"], ["XY"]], ["X", "Y", "Z"]),
@@ -203,15 +209,23 @@ class MultiPaxos(Protocol):
                            ["bar", "baz"]),
     }
 
-    def __init__(self, servers: int = 3, clients: int = 2, workload: str = "append-xy"):
+    def __init__(self, servers: int = 3, clients: int = 2, workload: str = "append-xy", mutant=0):
         cmds, exp, tokens = self.WORKLOADS[workload]
         self.workload = workload
+        self.mutant = self.mutant_id(mutant)
         self.servers = servers
         self.clients = clients
         self.tokens = tokens
         self.cmds = [[self._parse_cmd(c) for c in cl] for cl in cmds[:clients]]
         self.expected = exp[:clients]
         self.addresses = [f"server{i}" for i in range(1, servers + 1)] + [f"client{i}" for i in range(1, clients + 1)]
+
+    @classmethod
+    def mutant_id(cls, mutant) -> int:
+        m = cls.MUTANTS[mutant] if isinstance(mutant, str) else int(mutant)
+        if m not in cls.MUTANTS.values():
+            raise ValueError(f"unknown mutant {mutant!r}: {sorted(cls.MUTANTS)}")
+        return m
 
     @staticmethod
     def _parse_cmd(t: str):
@@ -256,7 +270,8 @@ class MultiPaxos(Protocol):
             vals = [0 if v is None else self.tokens.index(v) + 1 for _, v in cl] + [0] * (3 - len(cl))
             e = [self.encode_result(cl[k][0], x) for k, x in enumerate(exp)] + [-1] * (3 - len(exp))
             ps += [len(cl)] + ops + vals + e
-        return ps
+        # the mutant goes last and only when set: the protocol's own vector is what it always was
+        return ps + [self.mutant] if self.mutant else ps
 
     def kv_code(self, cmd: str) -> int:
         """A KV command as hasCommand's code: a workload command ("APPEND:foo:X", "PUT:foo:bar",
@@ -888,20 +903,22 @@ class MultiPaxosIR(IRProtocol):
     with MultiPaxos's workloads (the same command tables and result encodings) and predicates
     (LOGS_CONSISTENT_ALL_SLOTS, LOGS_CONSISTENT, APPENDS_LINEARIZABLE and the ClientWorker family)."""
 
-    def __init__(self, servers: int = 3, clients: int = 2, workload: str = "append-xy"):
-        mp = MultiPaxos(servers, clients, workload)
+    def __init__(self, servers: int = 3, clients: int = 2, workload: str = "append-xy", mutant=0):
+        mp = MultiPaxos(servers, clients, workload, mutant)
         ps = mp.params()[2:]  # per client: ncmds, ops[3], vals[3], expected[3]
         self._tables = {"ncmd": [[ps[10 * c]] for c in range(2)],
                         "op": [ps[10 * c + 1: 10 * c + 4] for c in range(2)],
                         "val": [ps[10 * c + 4: 10 * c + 7] for c in range(2)],
-                        "expected": [ps[10 * c + 7: 10 * c + 10] for c in range(2)]}
+                        "expected": [ps[10 * c + 7: 10 * c + 10] for c in range(2)],
+                        "mutant": [[mp.mutant]]}  # MultiPaxos's mutants, after the existing parameters
         super().__init__("multipaxos", servers=servers, clients=clients)
         self.mp = mp
         self.workload = workload
+        self.mutant = mp.mutant
 
     def params(self):
         ps = super().params()
-        for n in ("ncmd", "op", "val", "expected"):
+        for n in ("ncmd", "op", "val", "expected", "mutant"):
             for row in self._tables[n]:
                 ps += row
         return ps

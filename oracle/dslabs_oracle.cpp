@@ -13,6 +13,8 @@
 //   --inv NAME / --goal NAME / --prune NAME   (repeatable, insertion order kept; prefix "!" = negate)
 //   --max-depth N, --finish-level (level-synchronous terminal rule), --max-secs S,
 //   --no-timers ADDR, --partition a,b|c (link filter), --print-states
+//   --watch NAME (repeatable): counted per depth over the discovered states ("watch_counts")
+//   --mutant adopt-chosen-only|accept-stale (multipaxos; proto_multipaxos.hpp)
 #include <cstring>
 #include <fstream>
 #include <iostream>
@@ -162,6 +164,7 @@ static Scenario build(const Args& a) {
   } else if (a.proto == "multipaxos") {
     multipaxos::Config cfg = multipaxos::Config::fromArgs(a.geti("servers", 3), a.geti("clients", 2),
                                                           a.get("workload", "append-xy"), false);
+    cfg.mutant = multipaxos::mutantByName(a.get("mutant", ""));
     sc.init = multipaxos::initial(cfg, sc.names);
     sc.pred = [common, cfg](const std::string& n) -> Predicate {
       auto p = common(n);
@@ -169,6 +172,7 @@ static Scenario build(const Args& a) {
       if (n == "LOGS_CONSISTENT_ALL_SLOTS") return multipaxos::logsConsistent(cfg);
       if (n == "LOGS_CONSISTENT") return multipaxos::logsConsistent(cfg, true);
       if (n == "APPENDS_LINEARIZABLE") return multipaxos::appendsLinearizable(cfg);
+      if (n == "CHOSEN_CONFLICT") return multipaxos::chosenConflict(cfg);
       auto parts = split(n, ':');
       if (parts[0] == "slotValid" && parts.size() == 2) return multipaxos::slotValidPred(cfg, std::stoi(parts[1]));
       if (parts[0] == "hasStatus" && parts.size() == 4) {  // hasStatus:serverK:slot:STATUS
@@ -274,6 +278,7 @@ static Settings settingsFrom(const Args& a, Scenario& sc) {
   for (auto& n : a.all("inv")) st.invariants.push_back(mk(n));
   for (auto& n : a.all("goal")) st.goals.push_back(mk(n));
   for (auto& n : a.all("prune")) st.prunes.push_back(mk(n));
+  for (auto& n : a.all("watch")) st.watches.push_back(mk(n));
   st.maxDepth = a.geti("max-depth", -1);
   for (auto& n : a.all("no-timers")) st.timersActive[addrOf(sc.names, n)] = false;
   for (auto& n : a.all("inactive")) {  // TestSettings.nodeActive(n, false)
@@ -381,7 +386,18 @@ static int runBfs(const Args& a) {
     if (i) std::cout << ",";
     printTerminal(R.terminals[i], sc.names, a.has("print-states"));
   }
-  std::cout << "],\"num_terminals\":" << R.terminals.size() << "}" << std::endl;
+  std::cout << "],\"num_terminals\":" << R.terminals.size();
+  if (!st.watches.empty()) {  // --watch P: per watch, the states of each depth that hold it
+    std::cout << ",\"watch_counts\":[";
+    for (size_t i = 0; i < R.watchCounts.size(); i++) {
+      std::cout << (i ? ",[" : "[");
+      for (size_t d = 0; d < R.perDepth.size(); d++)
+        std::cout << (d ? "," : "") << (d < R.watchCounts[i].size() ? R.watchCounts[i][d] : 0);
+      std::cout << "]";
+    }
+    std::cout << "]";
+  }
+  std::cout << "}" << std::endl;
   return 0;
 }
 

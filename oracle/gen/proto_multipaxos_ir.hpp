@@ -13,6 +13,7 @@ struct Params {
   int op[2][3] = {};
   int val[2][3] = {};
   int expected[2][3] = {};
+  int mutant[1][1] = {};
 };
 // Params from the engine's parameter vector (dsl_protocol_desc.params order)
 inline Params from_vector(const std::vector<long long>& v) {
@@ -30,6 +31,8 @@ inline Params from_vector(const std::vector<long long>& v) {
     for (int c = 0; c < 3; c++, q++) p.val[r][c] = q < v.size() ? (int)v[q] : 0;
   for (int r = 0; r < 2; r++)
     for (int c = 0; c < 3; c++, q++) p.expected[r][c] = q < v.size() ? (int)v[q] : -1;
+  for (int r = 0; r < 1; r++)
+    for (int c = 0; c < 1; c++, q++) p.mutant[r][c] = q < v.size() ? (int)v[q] : 0;
   return p;
 }
 // node index of a kind's first instance: kinds in declaration order, instances consecutive
@@ -322,7 +325,7 @@ struct N_server : Node {
         if (((l_me221 & 3) == 2)) {
           p1blog[0] = ((2 | (0 << 2)) | (((l_me221 >> 8) & 7) << 8));
         } else {
-          if (((((l_me221 & 3) == 1) && ((l_mm222 & 3) != 2)) && (((l_mm222 & 3) == 0) || (((l_mm222 >> 2) & 63) < ((l_me221 >> 2) & 63))))) {
+          if (((((prm.mutant[0][0] != 1) && ((l_me221 & 3) == 1)) && ((l_mm222 & 3) != 2)) && (((l_mm222 & 3) == 0) || (((l_mm222 >> 2) & 63) < ((l_me221 >> 2) & 63))))) {
             p1blog[0] = l_me221;
           }
         }
@@ -331,7 +334,7 @@ struct N_server : Node {
         if (((l_me223 & 3) == 2)) {
           p1blog[1] = ((2 | (0 << 2)) | (((l_me223 >> 8) & 7) << 8));
         } else {
-          if (((((l_me223 & 3) == 1) && ((l_mm224 & 3) != 2)) && (((l_mm224 & 3) == 0) || (((l_mm224 >> 2) & 63) < ((l_me223 >> 2) & 63))))) {
+          if (((((prm.mutant[0][0] != 1) && ((l_me223 & 3) == 1)) && ((l_mm224 & 3) != 2)) && (((l_mm224 & 3) == 0) || (((l_mm224 >> 2) & 63) < ((l_me223 >> 2) & 63))))) {
             p1blog[1] = l_me223;
           }
         }
@@ -340,7 +343,7 @@ struct N_server : Node {
         if (((l_me225 & 3) == 2)) {
           p1blog[2] = ((2 | (0 << 2)) | (((l_me225 >> 8) & 7) << 8));
         } else {
-          if (((((l_me225 & 3) == 1) && ((l_mm226 & 3) != 2)) && (((l_mm226 & 3) == 0) || (((l_mm226 >> 2) & 63) < ((l_me225 >> 2) & 63))))) {
+          if (((((prm.mutant[0][0] != 1) && ((l_me225 & 3) == 1)) && ((l_mm226 & 3) != 2)) && (((l_mm226 & 3) == 0) || (((l_mm226 >> 2) & 63) < ((l_me225 >> 2) & 63))))) {
             p1blog[2] = l_me225;
           }
         }
@@ -349,7 +352,7 @@ struct N_server : Node {
         if (((l_me227 & 3) == 2)) {
           p1blog[3] = ((2 | (0 << 2)) | (((l_me227 >> 8) & 7) << 8));
         } else {
-          if (((((l_me227 & 3) == 1) && ((l_mm228 & 3) != 2)) && (((l_mm228 & 3) == 0) || (((l_mm228 >> 2) & 63) < ((l_me227 >> 2) & 63))))) {
+          if (((((prm.mutant[0][0] != 1) && ((l_me227 & 3) == 1)) && ((l_mm228 & 3) != 2)) && (((l_mm228 & 3) == 0) || (((l_mm228 >> 2) & 63) < ((l_me227 >> 2) & 63))))) {
             p1blog[3] = l_me227;
           }
         }
@@ -363,7 +366,7 @@ struct N_server : Node {
       handled = true;
       [&]() {
         const int l_b = ((std::stoi(m.f[0]) << 2) | std::stoi(m.f[1]));
-        if ((l_b < ((round << 2) | leader))) {
+        if (((l_b < ((round << 2) | leader)) && (prm.mutant[0][0] != 2))) {
           return;
         }
         if ((l_b > ((round << 2) | leader))) {
@@ -806,7 +809,7 @@ struct N_server : Node {
             if (((l_me290 & 3) == 2)) {
               p1blog[0] = ((2 | (0 << 2)) | (((l_me290 >> 8) & 7) << 8));
             } else {
-              if (((((l_me290 & 3) == 1) && ((l_mm291 & 3) != 2)) && (((l_mm291 & 3) == 0) || (((l_mm291 >> 2) & 63) < ((l_me290 >> 2) & 63))))) {
+              if (((((prm.mutant[0][0] != 1) && ((l_me290 & 3) == 1)) && ((l_mm291 & 3) != 2)) && (((l_mm291 & 3) == 0) || (((l_mm291 >> 2) & 63) < ((l_me290 >> 2) & 63))))) {
                 p1blog[0] = l_me290;
               }
             }
@@ -815,7 +818,7 @@ struct N_server : Node {
             if (((l_me292 & 3) == 2)) {
               p1blog[1] = ((2 | (0 << 2)) | (((l_me292 >> 8) & 7) << 8));
             } else {
-              if (((((l_me292 & 3) == 1) && ((l_mm293 & 3) != 2)) && (((l_mm293 & 3) == 0) || (((l_mm293 >> 2) & 63) < ((l_me292 >> 2) & 63))))) {
+              if (((((prm.mutant[0][0] != 1) && ((l_me292 & 3) == 1)) && ((l_mm293 & 3) != 2)) && (((l_mm293 & 3) == 0) || (((l_mm293 >> 2) & 63) < ((l_me292 >> 2) & 63))))) {
                 p1blog[1] = l_me292;
               }
             }
@@ -824,7 +827,7 @@ struct N_server : Node {
             if (((l_me294 & 3) == 2)) {
               p1blog[2] = ((2 | (0 << 2)) | (((l_me294 >> 8) & 7) << 8));
             } else {
-              if (((((l_me294 & 3) == 1) && ((l_mm295 & 3) != 2)) && (((l_mm295 & 3) == 0) || (((l_mm295 >> 2) & 63) < ((l_me294 >> 2) & 63))))) {
+              if (((((prm.mutant[0][0] != 1) && ((l_me294 & 3) == 1)) && ((l_mm295 & 3) != 2)) && (((l_mm295 & 3) == 0) || (((l_mm295 >> 2) & 63) < ((l_me294 >> 2) & 63))))) {
                 p1blog[2] = l_me294;
               }
             }
@@ -833,7 +836,7 @@ struct N_server : Node {
             if (((l_me296 & 3) == 2)) {
               p1blog[3] = ((2 | (0 << 2)) | (((l_me296 >> 8) & 7) << 8));
             } else {
-              if (((((l_me296 & 3) == 1) && ((l_mm297 & 3) != 2)) && (((l_mm297 & 3) == 0) || (((l_mm297 >> 2) & 63) < ((l_me296 >> 2) & 63))))) {
+              if (((((prm.mutant[0][0] != 1) && ((l_me296 & 3) == 1)) && ((l_mm297 & 3) != 2)) && (((l_mm297 & 3) == 0) || (((l_mm297 >> 2) & 63) < ((l_me296 >> 2) & 63))))) {
                 p1blog[3] = l_me296;
               }
             }

@@ -416,6 +416,7 @@ struct Predicate {
 
 struct Settings {
   std::vector<Predicate> invariants, goals, prunes;
+  std::vector<Predicate> watches;  // counted per depth over the discovered states; they end nothing
   int maxDepth = -1;
   bool networkActive = true;
   std::map<std::pair<int, int>, bool> linkActive;
@@ -546,6 +547,7 @@ struct Results {
   int maxDepth = 0;
   std::vector<uint64_t> perDepth;  // unique states discovered per depth (initial state included)
   std::vector<Terminal> terminals;  // first = the one the reference would report first
+  std::vector<std::vector<uint64_t>> watchCounts;  // [watch][depth]: discovered states that hold it
   double elapsed = 0;
   uint64_t successorsGenerated = 0;
 };
@@ -570,7 +572,18 @@ inline Results bfs(std::shared_ptr<const State> init, const Settings& st, bool f
     R.states++;
     R.maxDepth = std::max(R.maxDepth, d);
   };
+  R.watchCounts.resize(st.watches.size());
+  auto watch = [&](const std::shared_ptr<const State>& s) {  // every counted state, terminal or not
+    if (s->exception) return;
+    for (size_t i = 0; i < st.watches.size(); i++) {
+      PredResult r = st.watches[i].test(*s);
+      if (r.threw || !r.value) continue;
+      if ((int)R.watchCounts[i].size() <= s->depth) R.watchCounts[i].resize(s->depth + 1, 0);
+      R.watchCounts[i][s->depth]++;
+    }
+  };
   auto check = [&](const std::shared_ptr<const State>& s) -> Status {
+    watch(s);
     if (s->exception) {
       R.terminals.push_back({End::EXCEPTION_THROWN, s, "", s->exceptionMsg});
       return Status::TERMINAL;

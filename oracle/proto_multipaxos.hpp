@@ -44,10 +44,24 @@ constexpr int kMaxSlots = 4;
 constexpr int kMaxRound = 15;
 constexpr int kTick = 100, kClientRetry = 100;
 
+// Protocol mutants (--mutant NAME), for fixtures that make the log invariants false:
+// adopt-chosen-only: phase 1 merges only CHOSEN entries (the candidate's own log and the P1b logs),
+//                    so a new leader can re-propose another command over an accepted one;
+// accept-stale:      an acceptor accepts a P2a of a ballot below its own (keeping its ballot) and
+//                    answers P2b, so a deposed leader can still gather a majority.
+enum Mutant { MUTANT_NONE = 0, MUTANT_ADOPT_CHOSEN_ONLY = 1, MUTANT_ACCEPT_STALE = 2 };
+inline int mutantByName(const std::string& n) {
+  if (n.empty() || n == "none" || n == "0") return MUTANT_NONE;
+  if (n == "adopt-chosen-only" || n == "1") return MUTANT_ADOPT_CHOSEN_ONLY;
+  if (n == "accept-stale" || n == "2") return MUTANT_ACCEPT_STALE;
+  throw std::runtime_error("unknown mutant " + n);
+}
+
 // Workloads are KVStoreWorkload command / result templates on the key "foo"
 // (labs/lab1-clientserver/tst/dslabs/kvstore/KVStoreWorkload.java:40-66, :76-133).
 struct Config {
   int servers = 3, clients = 2;
+  int mutant = MUTANT_NONE;
   std::vector<std::vector<std::string>> cmds;      // per client: "APPEND:foo:X" / "PUT:foo:bar" / "GET:foo"
   std::vector<std::vector<std::string>> expected;  // per client: expected results (may be empty)
   static Config fromArgs(int servers, int clients, const std::string& workload, bool) {
@@ -187,6 +201,7 @@ inline std::vector<Entry> parseLog(const std::string& s) {
 
 struct PaxosServer : Node {
   int me = 0, n = 3;
+  int mutant = MUTANT_NONE;  // a parameter, not state
   Ballot ballot;
   bool active = false, electing = false, heard = false;
   int missed = 0;
@@ -320,7 +335,8 @@ struct PaxosServer : Node {
       Entry& m = p1bLog[i];
       if (e.status == CHOSEN) {
         m = Entry{CHOSEN, Ballot{}, e.cmd};
-      } else if (e.status == ACCEPTED && m.status != CHOSEN && (m.status == EMPTY || m.ballot < e.ballot)) {
+      } else if (mutant != MUTANT_ADOPT_CHOSEN_ONLY && e.status == ACCEPTED && m.status != CHOSEN &&
+                 (m.status == EMPTY || m.ballot < e.ballot)) {  // adopt-chosen-only drops accepted entries
         m = e;
       }
     }
@@ -367,7 +383,8 @@ struct PaxosServer : Node {
       }
     } else if (m.type == "P2a") {
       Ballot b = Ballot::parse(m.f[0]);
-      if (b < ballot) return;
+      // accept-stale goes on with a lower ballot: adopt() leaves the ballot, the value is accepted
+      if (b < ballot && mutant != MUTANT_ACCEPT_STALE) return;
       adopt(b);
       heard = true;
       int slot = std::stoi(m.f[1]);
@@ -473,6 +490,7 @@ inline std::shared_ptr<State> initial(const Config& cfg, Names& names) {
     auto p = std::make_shared<PaxosServer>();
     p->me = s;
     p->n = cfg.servers;
+    p->mutant = cfg.mutant;
     nodes.push_back(p);
     kinds.push_back(Kind::Server);
   }
@@ -559,6 +577,23 @@ inline Predicate slotValidPred(const Config& cfg, int i) {
   return {"Logs consistent for slot " + std::to_string(i), [N, i](const State& s) {
             PredResult r;
             r.value = slotValid(s, N, i, &r.detail);
+            return r;
+          }};
+}
+// Two servers hold CHOSEN entries with different commands in one slot (slotValid's "Two different
+// commands chosen" branch). Not a lab predicate: the fixture generators ask it of the mutants.
+inline Predicate chosenConflict(const Config& cfg) {
+  int N = cfg.servers;
+  return {"Two different commands chosen for a slot", [N](const State& s) {
+            PredResult r;
+            r.value = false;
+            for (int i = 1; i <= kMaxSlots; i++)
+              for (int a = 0; a < N; a++)
+                for (int b = a + 1; b < N; b++) {
+                  const PaxosServer *x = server(s, a), *y = server(s, b);
+                  if (x->status(i) == CHOSEN && y->status(i) == CHOSEN && !x->log[i].cmd.sameKv(y->log[i].cmd))
+                    r.value = true;
+                }
             return r;
           }};
 }

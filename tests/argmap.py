@@ -24,10 +24,10 @@ def protocol(args):
                        incorrect="--incorrect" in args)
     if p == "multipaxos_ir":  # tests give --servers / --clients / --workload (the oracle takes MultiPaxosIR.oracle_args())
         return MultiPaxosIR(int(_opt(args, "--servers", 3)), int(_opt(args, "--clients", 2)),
-                            _opt(args, "--workload", "append-xy"))
+                            _opt(args, "--workload", "append-xy"), mutant=_opt(args, "--mutant", "none"))
     if p == "multipaxos":
         return MultiPaxos(int(_opt(args, "--servers", 3)), int(_opt(args, "--clients", 2)),
-                          _opt(args, "--workload", "append-xy"))
+                          _opt(args, "--workload", "append-xy"), mutant=_opt(args, "--mutant", "none"))
     if p == "pb_ir":  # tests give --servers / --clients / --workload (the oracle takes PBIR.oracle_args())
         return PBIR(int(_opt(args, "--servers", 2)), int(_opt(args, "--clients", 1)), _opt(args, "--workload", "putget"))
     if p == "pb":

@@ -74,9 +74,26 @@ LAB0 = {
 }
 
 
-def gen(cases, fname):
-    out = {}
+def predicate_index(args, terminal):
+    """Index (in --inv / --goal order) of the predicate that ends the search at `terminal`: the first
+    invariant false or throwing, else the first goal true, when the oracle replays its trace and
+    evaluates every predicate in full; -1 for an exception."""
+    if terminal["kind"] not in ("INVARIANT_VIOLATED", "GOAL_FOUND"):
+        return -1
+    rep = oracle_util.replay([a for a in args if a != "--finish-level"], terminal["trace"])
+    assert rep["ok"] and rep["depth"] == terminal["depth"], rep
+    if terminal["kind"] == "INVARIANT_VIOLATED":
+        return next(i for i, x in enumerate(rep["invariants"]) if x["threw"] or not x["value"])
+    return next(i for i, x in enumerate(rep["goals"]) if x["value"] and not x["threw"])
+
+
+def gen(cases, fname, names=None):
+    """Regenerates the named cases (all by default), keeping the file's others."""
+    path = os.path.join(HERE, fname)
+    out = json.load(open(path)) if names and os.path.exists(path) else {}
     for name, c in cases.items():
+        if names and name not in names:
+            continue
         r = oracle_util.run("bfs", c["args"], timeout=c.get("timeout", 600))
         if r.get("terminals"):
             t = r["terminals"]
@@ -86,9 +103,14 @@ def gen(cases, fname):
                      "terminal_depth": r.get("terminal_depth", -1),
                      "terminal_kinds": sorted({t["kind"] for t in r.get("terminals", [])}),
                      "terminals": r.get("terminals", [])[:8]}
+        if "expect" in c:  # the mutants: what the case is for, checked where it is generated
+            assert (r["end"], r["terminals"][0]["predicate"]) == c["expect"], (name, r["end"], r["terminals"][:1])
+            out[name]["num_terminals"] = r["num_terminals"]
+            out[name]["predicate_index"] = predicate_index(c["args"], r["terminals"][0])
+            out[name]["predicate"] = r["terminals"][0]["predicate"]
         print(name, r["end"], r["states"], r["max_depth"])
-    with open(os.path.join(HERE, fname), "w") as f:
-        json.dump(out, f, indent=1)
+    with open(path, "w") as f:
+        json.dump({k: out[k] for k in cases if k in out}, f, indent=1)
 
 
 def gen_lab0_sip():
@@ -153,6 +175,32 @@ MULTIPAXOS = {
                           ["--prune", "CLIENTS_DONE", "--max-depth", "11"], pinned={}),
     "mp_xz_d8": dict(args=MP + ["--workload", "append-xz"] + INV3 + ["--max-depth", "8"], pinned={}),
 }
+
+# The two mutants (oracle --mutant): searches that end with a log invariant false. The
+# oracle evaluates every predicate in full on every state, so these pin the engine's incremental
+# judge, the reported predicate and the terminal count where the verdict is "violated".
+MUT1, MUT2 = ["--mutant", "adopt-chosen-only"], ["--mutant", "accept-stale"]
+INV_SV = ["--inv", "RESULTS_OK", "--inv", "APPENDS_LINEARIZABLE", "--inv", "slotValid:2", "--inv", "slotValid:1"]
+_LOGS = ("INVARIANT_VIOLATED", "Non-empty log slots consistent")
+_SLOT1 = ("INVARIANT_VIOLATED", "Logs consistent for slot 1")
+for _m, _mut in (("mut1", MUT1), ("mut2", MUT2)):
+    MULTIPAXOS["mp_%s_logs" % _m] = dict(args=MP + ["--workload", "append-xy"] + _mut + INV3 + ["--finish-level"],
+                                        pinned={}, expect=_LOGS)
+    # the violated predicate is the last of four: predicate_index 3
+    MULTIPAXOS["mp_%s_slotvalid" % _m] = dict(args=MP + ["--workload", "append-xy"] + _mut + INV_SV +
+                                             ["--finish-level"], pinned={}, expect=_SLOT1)
+MULTIPAXOS["mp_mut1_logs_active"] = dict(args=MP + ["--workload", "append-xy"] + MUT1 +
+                                         ["--inv", "LOGS_CONSISTENT", "--finish-level"], pinned={},
+                                         expect=("INVARIANT_VIOLATED", "Active log slots consistent"))
+# APPENDS_LINEARIZABLE alone is first false at depth 12. With every timer on that is 982,917 states;
+# server1 and the clients need no timer for it (server2 / server3 elect themselves on theirs, the
+# clients' requests are in the network from the start), and without them it is 483,782 states with
+# the same 8 terminals at depth 12, so the smaller setting is the fixture.
+MULTIPAXOS["mp_mut1_appends"] = dict(
+    args=MP + ["--workload", "append-xy"] + MUT1 + ["--inv", "APPENDS_LINEARIZABLE", "--no-timers", "server1",
+                                                   "--no-timers", "client1", "--no-timers", "client2",
+                                                   "--finish-level"],
+    pinned={}, expect=("INVARIANT_VIOLATED", "Sequence of appends to the same key is linearizable"))
 
 SY = ["--proto", "synthetic"]
 SYNTHETIC = {
@@ -312,6 +360,9 @@ if __name__ == "__main__":
         gen_lab0_sip()
     if "multipaxos" in which:
         gen(MULTIPAXOS, "multipaxos.json")
+    some = {w[len("multipaxos:"):] for w in which if w.startswith("multipaxos:")}  # e.g. multipaxos:mp_mut1_logs
+    if some:
+        gen(MULTIPAXOS, "multipaxos.json", some)
     if "synthetic" in which:
         gen(SYNTHETIC, "synthetic.json")
     if "amokv" in which:

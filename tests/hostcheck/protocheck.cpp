@@ -73,7 +73,7 @@ static int run(const dsl_protocol_desc& d, DevSettings set) {
   };
   std::vector<std::pair<long long, int>> parent{{-1, -1}};
   long long first_term_parent = -2;
-  int first_term_event = -1;
+  int first_term_event = -1, first_term_pi = -1;
   auto key = [](const S& s) { return std::string((const char*)s.w, sizeof(S)); };
   S init;
   if (!init_state<P>(init.w, prm)) {
@@ -91,6 +91,7 @@ static int run(const dsl_protocol_desc& d, DevSettings set) {
   const char* end = "SPACE_EXHAUSTED";
   int tdepth = -1;
   long long nterm[3] = {0, 0, 0};
+  long long violating_judged = 0;  // invariant violations (full verdict) the incremental verdict was compared on
   long long fp_mismatch = 0, emit_mismatch = 0, judge_mismatch = 0, noop = 0, succ = 0, dup_sends = 0, skipped = 0, skip_mismatch = 0;
   if (v >= V_TERM_EXCEPTION) {
     end = v == V_TERM_INVARIANT ? "INVARIANT_VIOLATED" : "GOAL_FOUND";
@@ -162,11 +163,12 @@ static int run(const dsl_protocol_desc& d, DevSettings set) {
         int pi2 = -1;
         const int v2 = judge_view<P>(view, prm, set, d, &pi2, true);
         if (v2 != v || (v >= V_TERM_EXCEPTION && pi2 != pi)) judge_mismatch++;
+        if (v == V_TERM_INVARIANT) violating_judged++;
       }
       if (v >= V_TERM_EXCEPTION) {
         if (tdepth < 0) tdepth = d;
         if (d == tdepth) nterm[v - V_TERM_EXCEPTION]++;
-        if (first_term_parent == -2) first_term_parent = n.id, first_term_event = k;
+        if (first_term_parent == -2) first_term_parent = n.id, first_term_event = k, first_term_pi = pi;
         best = std::min(best, v);
         continue;
       }
@@ -179,8 +181,9 @@ static int run(const dsl_protocol_desc& d, DevSettings set) {
     end = best == V_TERM_EXCEPTION ? "EXCEPTION_THROWN" : best == V_TERM_INVARIANT ? "INVARIANT_VIOLATED" : "GOAL_FOUND";
   unsigned long long total = 0;
   printf("{\"end\":\"%s\",\"terminal_depth\":%d,\"state_bytes\":%d,\"fp_mismatch\":%lld,\"emit_mismatch\":%lld,"
-         "\"judge_mismatch\":%lld,\"dup_sends\":%lld,\"skip_mismatch\":%lld,\"skipped\":%lld,\"per_depth\":[", end, tdepth,
-         (int)sizeof(S), fp_mismatch, emit_mismatch, judge_mismatch, dup_sends, skip_mismatch, skipped);
+         "\"judge_mismatch\":%lld,\"violating_judged\":%lld,\"predicate_index\":%d,\"dup_sends\":%lld,"
+         "\"skip_mismatch\":%lld,\"skipped\":%lld,\"per_depth\":[", end, tdepth, (int)sizeof(S), fp_mismatch, emit_mismatch,
+         judge_mismatch, violating_judged, first_term_pi, dup_sends, skip_mismatch, skipped);
   for (size_t i = 0; i < per.size(); i++) {
     printf("%s%llu", i ? "," : "", per[i]);
     total += per[i];
@@ -352,6 +355,9 @@ int main(int argc, char** argv) {
     lists[which][(*counts[which])++] = DevProg{(int16_t)start, (int16_t)(set.n_ops - start)};
   }
   set.max_depth = atoi(argv[argc - 1]);
+  // one leaf per program: the engine's flat judge (resolve_settings), the only one that passes `held`
+  // to P::eval_held -- the incremental verdict compared below is then the kernels' own
+  set.flat = set.n_ops == set.n_inv + set.n_goal + set.n_prune ? 1 : 0;
   switch (d.protocol) {
     case DSL_PROTO_PINGPONG: return run<PingPong>(d, set);
     case DSL_PROTO_SIPAXOS: return run<SIPaxos>(d, set);

@@ -14,9 +14,9 @@ from dslabs_amd.protocols import MultiPaxos
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def mp(servers, clients, workload):
+def mp(servers, clients, workload, mutant=0):
     """protocheck's protocol arguments for Multi-Paxos: the id, then the engine's parameters."""
-    return [5] + MultiPaxos(servers, clients, workload).params()
+    return [5] + MultiPaxos(servers, clients, workload, mutant).params()
 
 
 _MP3 = ["--inv", "RESULTS_OK", "--inv", "LOGS_CONSISTENT_ALL_SLOTS", "--inv", "APPENDS_LINEARIZABLE"]
@@ -137,6 +137,38 @@ def test_encoding_matches_oracle(protocheck, name):
     assert got["fp_mismatch"] == 0 and got["emit_mismatch"] == 0 and got["judge_mismatch"] == 0
     assert got["dup_sends"] == 0
     assert got["skip_mismatch"] == 0  # every event k_level skips (NoopFilter) is a true no-op
+
+
+# The Multi-Paxos mutants (tests/golden/multipaxos.json): searches that END with a log
+# invariant false. (protocheck invariants, the fixture whose arguments the live oracle gets)
+_SV = [1, 300, "402:2", "402:1"]  # RESULTS_OK, APPENDS_LINEARIZABLE, slotValid:2, slotValid:1
+MUTANT_CASES = {
+    "mp_mut1_logs": (1, [1, 400, 300]), "mp_mut1_slotvalid": (1, _SV),
+    "mp_mut2_logs": (2, [1, 400, 300]), "mp_mut2_slotvalid": (2, _SV),
+}
+with open(os.path.join(ROOT, "tests", "golden", "multipaxos.json")) as _f:
+    _MPG = json.load(_f)
+
+
+@pytest.mark.parametrize("name", sorted(MUTANT_CASES))
+def test_mutant_violation_is_judged_incrementally(protocheck, name):
+    """The incremental verdict (logs_consistent_held over the changed slots, the per-predicate read
+    sets) against the full evaluation where the full verdict is a VIOLATION: compared on at least
+    one successor, never different; and the end, the level and the predicate are the oracle's."""
+    mutant, invs = MUTANT_CASES[name]
+    case = _MPG[name]
+    assert MultiPaxos.MUTANTS[case["args"][case["args"].index("--mutant") + 1]] == mutant
+    got = run(protocheck, mp(3, 2, "append-xy", mutant) + ["--"] + invs + ["/", "/", -1])
+    want = oracle_util.run("bfs", case["args"], timeout=600)
+    assert got["end"] == want["end"] == "INVARIANT_VIOLATED"
+    assert got["per_depth"] == want["per_depth"] == case["per_depth"]
+    assert got["terminal_depth"] == want["terminals"][0]["depth"] == case["terminal_depth"]
+    assert got["terminals_at_depth"] == [0, want["num_terminals"], 0]
+    assert got["predicate_index"] == case["predicate_index"]
+    assert want["terminals"][0]["predicate"] == case["predicate"]
+    assert got["judge_mismatch"] == 0 and got["violating_judged"] > 0
+    assert got["fp_mismatch"] == 0 and got["emit_mismatch"] == 0 and got["dup_sends"] == 0
+    assert got["skip_mismatch"] == 0  # accept-stale delivers the stale P2a the protocol's filter skips
 
 
 @pytest.mark.parametrize("form", ["vstest", "vstest_ir"])

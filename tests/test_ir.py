@@ -107,19 +107,21 @@ def test_ir_amokv_device_form_on_cpu(name):
 
 # ---- lab3 Multi-Paxos (BASELINE C5's protocol) from the IR: dslabs_amd/ir/specs/multipaxos.py ------------------
 MP = json.load(open(os.path.join(HERE, "golden", "multipaxos.json")))
-# the IR oracle runs the whole C5 d12 space in minutes: it gets d8, the CPU BFS below d12
-MP_ORACLE = sorted(n for n in MP if n != "mp_c5_d12")
+# the IR oracle runs the whole C5 d12 space in minutes: it gets d8, the CPU BFS below d12; likewise
+# the mutant's 483,782 states of mp_mut1_appends (the IR oracle runs its smaller mutant fixtures)
+MP_ORACLE = sorted(n for n in MP if n not in ("mp_c5_d12", "mp_mut1_appends"))
 
 
 def _mp_ir(args):
-    """The IR protocol for a multipaxos fixture's --servers / --clients / --workload, and the rest of
-    its arguments (predicates, settings)."""
+    """The IR protocol for a multipaxos fixture's --servers / --clients / --workload / --mutant, and
+    the rest of its arguments (predicates, settings)."""
     from dslabs_amd.protocols import MultiPaxosIR
     opt = lambda n, d: args[args.index(n) + 1] if n in args else d  # noqa: E731
-    proto = MultiPaxosIR(int(opt("--servers", 3)), int(opt("--clients", 2)), opt("--workload", "append-xy"))
+    proto = MultiPaxosIR(int(opt("--servers", 3)), int(opt("--clients", 2)), opt("--workload", "append-xy"),
+                         mutant=opt("--mutant", "none"))
     rest, i = [], 0
     while i < len(args):
-        if args[i] in ("--proto", "--servers", "--clients", "--workload"):
+        if args[i] in ("--proto", "--servers", "--clients", "--workload", "--mutant"):
             i += 2
             continue
         rest.append(args[i])
@@ -136,6 +138,12 @@ def test_ir_multipaxos_oracle_matches_golden(name):
     r = oracle_util.run("bfs", proto.oracle_args() + rest, timeout=600)
     assert r["end"] == case["end"]
     assert r["per_depth"] == case["per_depth"]  # with --finish-level: the terminal's depth is the last one
+    if "num_terminals" in case:  # the mutants: the violation's depth, the terminals of its level, the predicate
+        assert r["terminals"][0]["depth"] == case["terminal_depth"] == len(case["per_depth"]) - 1
+        assert r["num_terminals"] == case["num_terminals"]
+        rep = oracle_util.replay(proto.oracle_args() + [a for a in rest if a != "--finish-level"], r["terminals"][0]["trace"])
+        assert rep["ok"] and rep["depth"] == case["terminal_depth"]
+        assert [i for i, x in enumerate(rep["invariants"]) if not x["value"]] == [case["predicate_index"]]
 
 
 @pytest.mark.parametrize("name", sorted(MP))
@@ -171,6 +179,27 @@ def test_ir_multipaxos_device_form_host_bfs(protocheck, servers, clients, worklo
 
 
 # ---- lab2 primary-backup + ViewServer (BASELINE C4's protocol) from the IR: dslabs_amd/ir/specs/pb.py ---------
+@pytest.mark.parametrize("invs,index", [([1, 400, 300], 1), ([401], 0), ([1, 300, "402:2", "402:1"], 3)],
+                         ids=["logs", "logs_active", "slotvalid"])
+@pytest.mark.parametrize("mutant", [1, 2])
+def test_ir_multipaxos_mutants_host_bfs(protocheck, mutant, invs, index):  # noqa: F811
+    """The mutants (the spec's last parameter) in the exact host BFS: the generated handlers and the
+    generated log predicates where they are FALSE against the hand-written ones -- the level, its
+    terminals, the predicate's index -- and the incremental judge against the full one on the
+    violating successors."""
+    from dslabs_amd.protocols import MultiPaxos, MultiPaxosIR
+    tail = ["--"] + invs + ["/", "/", -1]
+    got = run(protocheck, [10] + MultiPaxosIR(3, 2, "append-xy", mutant).params() + tail)
+    want = run(protocheck, [5] + MultiPaxos(3, 2, "append-xy", mutant).params() + tail)
+    assert got["end"] == want["end"] == "INVARIANT_VIOLATED"
+    assert got["per_depth"] == want["per_depth"] == MP["mp_mut%d_logs" % mutant]["per_depth"]
+    assert got["terminal_depth"] == want["terminal_depth"] and got["terminals_at_depth"] == want["terminals_at_depth"]
+    assert got["predicate_index"] == want["predicate_index"] == index
+    assert got["judge_mismatch"] == 0 and got["violating_judged"] > 0
+    assert got["fp_mismatch"] == 0 and got["emit_mismatch"] == 0 and got["dup_sends"] == 0
+    assert got["skip_mismatch"] == 0 and got["skipped"] > 0
+
+
 PBG = json.load(open(os.path.join(HERE, "golden", "pb.json")))
 _PB_LEAF = r"(hasViewReply|viewRepliesSent)(:[^,()]+)"
 

@@ -90,6 +90,44 @@ def test_amokv_oracle_matches_fixture(name):
     assert r["per_depth"] == case["per_depth"]
 
 
+MPG = _load("multipaxos.json")
+# the mutants' fixtures (make_golden.py: "expect"); mp_mut1_appends takes the oracle a minute
+MP_MUTANTS = sorted(n for n in MPG if "--mutant" in MPG[n]["args"] and n != "mp_mut1_appends")
+
+
+@pytest.mark.parametrize("name", MP_MUTANTS)
+def test_multipaxos_mutant_oracle_matches_fixture(name):
+    """A Multi-Paxos mutant ends with a log invariant false: the level, its terminals and the
+    predicate, whose index is that of the first invariant false when the trace is replayed."""
+    case = MPG[name]
+    r = oracle_util.run("bfs", case["args"], timeout=300)
+    assert r["end"] == case["end"] == "INVARIANT_VIOLATED"
+    assert r["per_depth"] == case["per_depth"] and r["states"] == case["states"]
+    assert r["num_terminals"] == case["num_terminals"] == 4
+    t = r["terminals"][0]
+    assert t["depth"] == case["terminal_depth"] == len(case["per_depth"]) - 1
+    assert t["predicate"] == case["predicate"]
+    rep = oracle_util.replay([a for a in case["args"] if a != "--finish-level"], t["trace"])
+    assert rep["ok"] and rep["depth"] == t["depth"]
+    false = [i for i, x in enumerate(rep["invariants"]) if x["threw"] or not x["value"]]
+    assert false == [case["predicate_index"]] and rep["invariants"][false[0]]["name"] == case["predicate"]
+
+
+def test_multipaxos_mutant_fixtures_differ_from_the_protocol():
+    """The mutants change the protocol where the issue says: adopt-chosen-only first at depth 6 (a
+    candidate's merge), accept-stale already at depth 4 (211 states against 207) -- the handlers are
+    pinned per depth, not only the judge -- and the unmutated fixtures are what they were."""
+    c5 = MPG["mp_c5_d8"]["per_depth"]
+    m1, m2 = MPG["mp_mut1_logs"]["per_depth"], MPG["mp_mut2_logs"]["per_depth"]
+    assert m1[:6] == c5[:6] and m1[6] != c5[6]
+    assert m2[:4] == c5[:4] and (m2[4], c5[4]) == (211, 207)
+    for a, b in (("mp_mut1_logs", "mp_mut1_slotvalid"), ("mp_mut2_logs", "mp_mut2_slotvalid"),
+                 ("mp_mut1_logs", "mp_mut1_logs_active")):
+        assert MPG[a]["per_depth"] == MPG[b]["per_depth"]  # one level ends them all: slot 1, chosen with no majority
+    assert MPG["mp_mut1_slotvalid"]["predicate_index"] == MPG["mp_mut2_slotvalid"]["predicate_index"] == 3
+    assert MPG["mp_mut1_appends"]["terminal_depth"] == 12 and MPG["mp_mut1_appends"]["num_terminals"] == 8
+
+
 PBG = _load("pb.json")
 
 

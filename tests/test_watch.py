@@ -16,7 +16,7 @@ import oracle_util
 import watch_cases
 from dslabs_amd import CLIENTS_DONE, NONE_DECIDED, RESULTS_OK, SearchSettings, _lib
 from dslabs_amd import search as S
-from dslabs_amd.protocols import MultiPaxosIR, PingPongIR
+from dslabs_amd.protocols import MultiPaxos, MultiPaxosIR, PingPongIR
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -182,6 +182,22 @@ def test_host_census_agrees_with_itself_and_the_fixture(census, name):
     assert all(len(c) == len(row["per_depth"]) for c in row["census"])
     assert all(t > 0 for t in row["true"])  # every watch of every case is reachable: each was true somewhere
     assert all(0 <= c <= n for vec in row["census"] for c, n in zip(vec, row["per_depth"]))
+
+
+@pytest.mark.parametrize("cls", [MultiPaxos, MultiPaxosIR], ids=lambda c: c.__name__)
+def test_host_census_of_the_mutant_is_the_oracles(watchcheck, cls):
+    """mp_mut1_watch_logs: the log predicates FALSE, counted per depth by the oracle (which evaluates
+    them in full) and by the host-compiled device predicates, on both forms of the protocol."""
+    gold = watch_cases.gold("mp_mut1_watch_logs")
+    proto, settings, state = watch_cases.mut1_watch_logs(cls)
+    row = watch_cases.watchcheck_run(watchcheck, "mp_mut1_watch_logs", proto, settings, state)
+    assert row["mismatch"] == 0 and row["errors"] == 0 and row["search_changed"] == 0
+    assert row["per_depth"] == gold["per_depth"] and row["census"] == gold["census"]
+    assert gold["watches"] == watch_cases.MUT_WATCHES
+    # the first violation (depth 8: chosen without a majority) and, deeper, conflicting chosen commands
+    assert gold["census"][0][:8] == [0] * 8 and gold["census"][0][8] > 0
+    assert sum(gold["chosen_conflict"]) > 0
+    assert all(a >= b for a, b in zip(gold["census"][0], gold["census"][1]))  # an invalid slot 1 is an inconsistent log
 
 
 def test_fixture_per_depth_is_the_oracle_fixtures():

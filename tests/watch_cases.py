@@ -129,6 +129,27 @@ CASES = {
     "pb_2s1c_d6": _pb,
 }
 
+# ---- lab3 with the adopt-chosen-only mutant: the log predicates false, counted by the ORACLE ---------------
+# No invariants, so the search goes on past the first violation (depth 8, no majority) into states
+# where two servers hold different CHOSEN commands in a slot (depth 10): slotValid's other false branch.
+# Its census in watch.json is the oracle's (`bfs --watch`, every predicate evaluated in full), not
+# watchcheck's: tests/golden/make_watch_golden.py. APPENDS_LINEARIZABLE is not yet false by depth 10.
+MUT_WATCHES = ["!LOGS_CONSISTENT_ALL_SLOTS", "!slotValid:1", "!slotValid:2", "!APPENDS_LINEARIZABLE"]
+MUT_ORACLE_ARGS = ["--proto", "multipaxos", "--workload", "append-xy", "--mutant", "adopt-chosen-only",
+                   "--max-depth", "10"]
+
+
+def mut1_watch_logs(cls=MultiPaxos):
+    """(protocol, settings, None) of mp_mut1_watch_logs on MultiPaxos or MultiPaxosIR."""
+    proto = cls(3, 2, "append-xy", mutant="adopt-chosen-only")
+    s = _settings(22).maxDepth(10)
+    for name in MUT_WATCHES:
+        s.addWatch(argmap.predicate(proto, name))
+    return proto, s, None
+
+
+ORACLE_CASES = {"mp_mut1_watch_logs": mut1_watch_logs}
+
 # (case, watch index) -> (first depth, states holding the watch there): the committed oracle's
 # `bfs --goal P --finish-level` (max_depth of the result, num_terminals), ORACLE_ARGS below
 ANCHORS = {
